@@ -6,12 +6,18 @@
     python bench.py --mode infer --dtype bf16        # BASELINE configs[4]: generator_A2B, bs=16, 80x512
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --full                           # + traced-step roofline, CPU baseline, nested configs[2..4], sync-losses, post-cut-off
+    python bench.py --dump-outputs DIR               # + the timed path's outputs as DIR/<name>.npy (see replay_outputs)
 
 A "step" = one full iteration of the reference's inner loop (train.py:195-299: 10 generator forwards,
 12 discriminator forwards, both backward passes, both Adam steps) on one synthetic minibatch per GPU
 (bs=1, 80 mel x 64 frames, fp32 -- BASELINE.json configs[1]); inputs are resident in HBM before the
 timed region.  Prints ONE JSON line on rank 0.  `value` is the whole-job rate: per-GPU bs=1 iterations
 per second summed over the N data-parallel ranks (weak scaling).
+
+A plain run sets up, warms up, times exactly --steps steps, writes --dump-outputs and prints the line.
+Everything measured beside the headline (the per-launch trace with its roofline / per-kernel figures,
+the CPU oracle baseline and parity probe, the nested configurations) runs only with --full.
 """
 import argparse
 import ctypes
@@ -38,6 +44,9 @@ PEAK_HBM_GBS = 8000.0
 # 2.07 GB (7 words x 73.9 M live parameters), at the tabulated batch sizes
 ALG_BYTES_PER_ITER = {1: 4.9e9 + 2.07e9, 8: 18.4e9 + 2.07e9, 32: 64.7e9 + 2.07e9}
 INFER_GFLOP_PER_SAMPLE_64 = 19.676     # generator forward, conv MAC*2, per sample of 64 frames
+DUMP_SAMPLE = 1 << 20                  # --dump-outputs: parameters kept per network (a fixed, seeded sample of its flat parameter vector)
+DUMP_MAX_BYTES = 64 << 20
+REPLAY_STEPS = 5                       # --dump-outputs, training: steps of the replay from the seeded start (replay_outputs)
 
 
 def cpu_model():
@@ -79,6 +88,35 @@ def build_nets(device):
     for i, n in enumerate(names):
         nets[n] = (Generator() if i < 2 else Discriminator()).to(device)
     return nets
+
+
+def param_sample(nets):
+    """Per network a seeded sample of DUMP_SAMPLE positions of its flat parameter vector (named_parameters order; the same positions in
+    every run), float32, on the device."""
+    out = {}
+    for name, net in nets.items():
+        flat = torch.cat([p.detach().reshape(-1) for p in net.parameters()])
+        idx = np.sort(np.random.default_rng(0).choice(flat.numel(), min(DUMP_SAMPLE, flat.numel()), replace=False))
+        out[name] = flat[torch.from_numpy(idx).to(flat.device)].float()
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: one DIR/<name>.npy per array (float32 / float64), DUMP_MAX_BYTES at most in all: an array beyond its equal
+    share of the budget is written as a fixed, seeded sample of its flattened elements (sorted positions, the same in every run)."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    share = DUMP_MAX_BYTES // len(arrays)
+    for k, a in list(arrays.items()):
+        if a.nbytes > share:
+            n = share // a.itemsize
+            arrays[k] = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+            log("outputs: %s sampled, %d of %d elements" % (k, n, a.size))
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    log("outputs: %d arrays, %.1f MB -> %s" % (len(arrays), total / 1e6, out_dir))
 
 
 def pmc_traffic(kernel, B):
@@ -177,7 +215,7 @@ def cpu_baseline(B, T, n_timed, first_losses, threads=0, warm=True):
             "host_cpus": os.cpu_count()}, parity
 
 
-def infer_record(args, rank, world, device, dtype, B, T, steps, warmup):
+def infer_record(args, rank, world, device, dtype, B, T, steps, warmup, config_id=None):
     """BASELINE configs[4]: generator_A2B inference (test.py path), bs=16, 80 mel x 512 frames, all-ones mask, weights = the seeded
     default init cast to the compute dtype.  A step = one batched forward; value = mel-frames/s = 16*512 / latency, summed over ranks
     (independent replicas: inference has no exchange step).  Returns the record on rank 0 (None elsewhere)."""
@@ -206,9 +244,21 @@ def infer_record(args, rank, world, device, dtype, B, T, steps, warmup):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     finite = bool(torch.isfinite(outs).all())
+    if args.dump_outputs and rank == 0 and config_id is None:
+        dump_outputs(args.dump_outputs, {"generator_A2B_out": outs.float().cpu().numpy()})
     if rank == 0:
         ms = 1e3 * dt / args.steps
         gflop = INFER_GFLOP_PER_SAMPLE_64 * (T / 64.0) * B
+        res = {"metric": "generator_A2B inference mel-frames/s, bs=%d x %d frames" % (B, T), "value": world * B * T * args.steps / dt,
+               "unit": "mel-frames/s (= batch x frames / latency, summed over GPUs)", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
+               "config": {"workload": "generator_A2B forward (test.py path), bs=%d, 80 mel x %d frames, all-ones mask, %s, default-init "
+                                      "weights (seed 0)" % (B, T, dtype), "global_batch": world * B, "parallelism": "replicas%d" % world},
+               "algorithmic_gflop_per_step": round(gflop, 1),               # direct-convolution FLOPs of the forward (SURVEY 8d)
+               "algorithmic_tflops": gflop / ms,
+               "outputs_finite": finite}
+        if not args.full:
+            return res
         peak = PEAK_BF16_MFMA_TFLOPS if dtype == "bf16" else PEAK_FP32_MFMA_TFLOPS
         # roofline of the DOMINANT kernel family of one traced forward, from the launchers' own EXECUTED FLOPs (the fp32 path runs its
         # 5x5 layers as Winograd products: 0.36x / 0.44x of the direct-convolution FLOPs, so "algorithmic FLOPs / time" can exceed the
@@ -229,19 +279,11 @@ def infer_record(args, rank, world, device, dtype, B, T, steps, warmup):
         kt = sum(r["ms"] for r in rows)
         dom = rows[0]
         ach = dom["gflop"] / dom["ms"]
-        res = {"metric": "generator_A2B inference mel-frames/s, bs=%d x %d frames" % (B, T), "value": world * B * T * args.steps / dt,
-               "unit": "mel-frames/s (= batch x frames / latency, summed over GPUs)", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
-               "config": {"workload": "generator_A2B forward (test.py path), bs=%d, 80 mel x %d frames, all-ones mask, %s, default-init "
-                                      "weights (seed 0)" % (B, T, dtype), "global_batch": world * B, "parallelism": "replicas%d" % world},
-               "roofline": {"bound": "mfma", "achieved": ach, "peak": peak, "unit": "TFLOP/s", "frac": ach / peak, "traffic": None,
-                            "kernel": dom["kernel"], "launches_per_step": dom["launches"], "avg_launch_ms": dom["ms"] / dom["launches"],
-                            "share_of_kernel_time": dom["ms"] / kt, "flops": "executed (as launched)"},
-               "kernel_time_ms_per_step": {r["kernel"]: round(r["ms"], 4) for r in rows},
-               "executed_gflop_per_step": round(sum(r["gflop"] for r in rows), 1),
-               "algorithmic_gflop_per_step": round(gflop, 1),               # direct-convolution FLOPs of the forward (SURVEY 8d)
-               "algorithmic_tflops": gflop / ms,
-               "outputs_finite": finite}
+        res["roofline"] = {"bound": "mfma", "achieved": ach, "peak": peak, "unit": "TFLOP/s", "frac": ach / peak, "traffic": None,
+                           "kernel": dom["kernel"], "launches_per_step": dom["launches"], "avg_launch_ms": dom["ms"] / dom["launches"],
+                           "share_of_kernel_time": dom["ms"] / kt, "flops": "executed (as launched)"}
+        res["kernel_time_ms_per_step"] = {r["kernel"]: round(r["ms"], 4) for r in rows}
+        res["executed_gflop_per_step"] = round(sum(r["gflop"] for r in rows), 1)
         if world == 1 and args.cpu_iters != 0:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import mcvc_oracle as orc
@@ -285,9 +327,15 @@ def parse_args():
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible mode (no floating-point atomics)")
     ap.add_argument("--batch-size", type=int, default=1, help="per-GPU minibatch (BASELINE metric: 1)")
     ap.add_argument("--frames", type=int, default=64)
-    ap.add_argument("--cpu-iters", type=int, default=-1, help="timed CPU-baseline iterations (0 = skip; default: about 10-30 s of CPU work)")
-    ap.add_argument("--no-trace", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="default single-GPU run: skip the nested records of BASELINE configs[2..4]")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: one traced step (roofline, per-kernel times, "
+                    "byte counts), the CPU oracle baseline + first-iteration parity, and -- single-GPU bs=1 training -- the nested records of "
+                    "BASELINE configs[2..4], the sync-losses price and the post-cut-off step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write the timed path's outputs as DIR/<name>.npy "
+                    "(training: the run's first steps replayed from the seeded start -- the last one's losses and every network's parameter change "
+                    "on a seeded sample of positions, see replay_outputs; inference: the last timed forward's output)")
+    ap.add_argument("--cpu-iters", type=int, default=-1, help="--full: timed CPU-baseline iterations (0 = skip; default: about 10-30 s of CPU work)")
+    ap.add_argument("--no-trace", action="store_true", help="--full: skip the traced step")
+    ap.add_argument("--no-extra-configs", action="store_true", help="--full single-GPU run: skip the nested records of BASELINE configs[2..4]")
     ap.add_argument("--sync-losses", action="store_true", help="read the CURRENT iteration's g_loss and d_loss on the host every step, as the "
                     "reference's .item() calls do (train.py:302-304): completes the iteration before the next one is issued (no pipelining)")
     ap.add_argument("--loss-lag", type=int, default=2, help="the per-step loss readback returns the iteration issued this many step()s earlier "
@@ -300,11 +348,15 @@ def parse_args():
     ap.add_argument("--test-force-residency", type=int, default=None, help=argparse.SUPPRESS)    # tests: engines claim this many persistent passes in flight
     ap.add_argument("--test-distinct-gpus", action="store_true", help=argparse.SUPPRESS)         # tests: skip the ranks-share-a-GPU switch
     ap.add_argument("--serial", action="store_true", help="one stream: no lanes, no auxiliary weight-gradient stream (A/B comparison, per-kernel profiling)")
-    ap.add_argument("--dump-trace", default=None, help="write one traced step's per-launch records (launch order) to this file")
+    ap.add_argument("--dump-trace", default=None, help="write one traced step's per-launch records (launch order) to this file (traces a step without --full too)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads for the CPU baseline (0 = min(host cores, 32))")
     a = ap.parse_args()
     if a.warmup is None:
         a.warmup = 100 if a.mode == "infer" else 10
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:
+        a.cpu_iters = 0                    # the CPU baseline is a --full measurement
     return a
 
 
@@ -319,24 +371,58 @@ def dist_info(world, device, force=False):
             "gpus_visible": torch.cuda.device_count()}
 
 
-def train_record(args, rank, world, device, B, T, steps, warmup, cpu_iters, n_batches, cpu_warm=True, config_id=None, stop_identity_after=1e4):
-    """One timed training configuration (a full G+D iteration at per-GPU batch B): W warm-up + exactly K timed steps between
-    barrier + synchronize pairs, max over ranks; then one traced step (per-kernel HIP events) for the roofline of the dominant kernel
-    family and the CPU oracle on a bounded sample of the same workload.  Returns the record on rank 0 (None elsewhere)."""
+def make_engine(args, world, device, B, T, stop_identity_after):
+    """(nets, schedule, reducer, engine) of the benchmark's training step: seeded default-init networks, the canonical schedule."""
     from mask_cyclegan_vc.engine import TrainEngine
     from mask_cyclegan_vc.parallel import FlatGradReducer
     from mask_cyclegan_vc.schedule import StepSchedule
-    log("bs=%d: building nets" % B)
     nets = build_nets(device)
     sched = StepSchedule(generator_lr=2e-4, discriminator_lr=1e-4, num_epochs=6172, n_samples=81, batch_size=B,
                          decay_after=2e5, stop_identity_after=stop_identity_after, world_size=world)     # bash_scripts/mask_cyclegan_train.sh
-    one_rank = bool(getattr(args, "rccl_one_rank", False))
-    dist_on = world > 1 or one_rank
-    reducer = FlatGradReducer(force=one_rank)
+    reducer = FlatGradReducer(force=bool(getattr(args, "rccl_one_rank", False)))
     engine = TrainEngine(nets, B, T, schedule=sched, reducer=reducer)
     engine.concurrent = not args.serial
     if args.serial:
         engine.aux_wgrad = False          # truly one stream: per-kernel durations comparable with the traced step's
+    return nets, sched, reducer, engine
+
+
+def replay_outputs(args, world, device, B, T, batches, stop_identity_after):
+    """--dump-outputs, training: the timed path once more after the timed region, from the benchmark's seeded starting state -- a fresh
+    engine (same construction, schedule, streams, arithmetic and per-step loss readback as the timed loop) runs the run's first
+    REPLAY_STEPS steps on the same batches.  Written: the losses of the last of them (float64) and, per network, the parameter change
+    p - p_init on the sampled positions (float32), which carries the Adam moments of several steps (the first update alone is
+    ~lr * sign(g)), the pipelined discriminator phase of step t beside the generator phase of step t+1 and the schedule.
+    Not the timed run's own final state: in the default mode (floating-point atomics) two runs differ by rounding, and since every
+    step feeds its parameters to the next the training loop lets that difference grow -- one pair of runs of W + K = 60 steps on an
+    MI355X ended ~1e-2 apart (rel-L2 of the parameters), with one stream as with the lanes -- so after a run of any useful length
+    nothing is comparable output for output.  A short replay from a fixed state is expected to stay at rounding level (the test
+    test_plain_single_gpu_bench_times_the_headline_only_and_dumps_its_outputs holds two runs to it and the replay to the CPU oracle).
+    Every rank runs it (the gradient exchange is collective); returns the arrays."""
+    sync_losses = bool(getattr(args, "sync_losses", False))
+    loss_lag = max(1, int(getattr(args, "loss_lag", 2)))
+    nets, _sched, _reducer, engine = make_engine(args, world, device, B, T, stop_identity_after)
+    p0 = param_sample(nets)
+    for i in range(REPLAY_STEPS):
+        engine.step(*batches[i % len(batches)])
+        engine.losses(lagged=0 if sync_losses else loss_lag)
+    final = engine.losses()                # completes the last step (a pending discriminator phase included)
+    out = {"loss_" + k: np.asarray(v, dtype=np.float64) for k, v in sorted(final.items())}
+    for name, p in param_sample(nets).items():
+        out["dparams_" + name] = (p - p0[name]).cpu().numpy()
+    del engine, nets
+    torch.cuda.empty_cache()
+    return out
+
+
+def train_record(args, rank, world, device, B, T, steps, warmup, cpu_iters, n_batches, cpu_warm=True, config_id=None, stop_identity_after=1e4):
+    """One timed training configuration (a full G+D iteration at per-GPU batch B): W warm-up + exactly K timed steps between
+    barrier + synchronize pairs, max over ranks; then one traced step (per-kernel HIP events) for the roofline of the dominant kernel
+    family and the CPU oracle on a bounded sample of the same workload.  Returns the record on rank 0 (None elsewhere)."""
+    log("bs=%d: building nets" % B)
+    one_rank = bool(getattr(args, "rccl_one_rank", False))
+    dist_on = world > 1 or one_rank
+    nets, sched, reducer, engine = make_engine(args, world, device, B, T, stop_identity_after)
     batches = synthetic_batches(n_batches, B, T, rank, device)
     log("engine ready; warm-up")
 
@@ -387,7 +473,8 @@ def train_record(args, rank, world, device, B, T, steps, warmup, cpu_iters, n_ba
     engine.check_faults()
     final = engine.losses()
     finite = all(np.isfinite(v) for v in final.values())
-    rows, raw = ([], []) if args.no_trace else trace_one_step(engine, batches)
+    traced = (args.full and not args.no_trace) or (args.dump_trace and config_id is None)
+    rows, raw = trace_one_step(engine, batches) if traced else ([], [])
     if args.dump_trace and rank == 0 and config_id is None and raw:
         with open(args.dump_trace, "w") as fh:
             for i, (k, ms, fl, by) in enumerate(raw):
@@ -412,6 +499,10 @@ def train_record(args, rank, world, device, B, T, steps, warmup, cpu_iters, n_ba
     engine._set_residency()
     del engine, nets
     torch.cuda.empty_cache()
+    if args.dump_outputs and config_id is None:
+        out = replay_outputs(args, world, device, B, T, batches, stop_identity_after)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, out)
     if rank != 0:
         return None
     ms = 1e3 * dt / steps
@@ -517,28 +608,30 @@ def main():
         if cpu_iters < 0:                  # bounded CPU sample: ~1 s per bs=1 iteration on 32 threads of the GPU box's host
             cpu_iters = max(2, min(12, 12 // B))
         res = train_record(args, rank, world, device, B, T, args.steps, args.warmup, cpu_iters, args.n_batches)
-        # The default single-GPU invocation (the one the driver runs) also measures the other BASELINE configs, each as a nested record
-        # with its own roofline and CPU sample: configs[2] = the bs=32 step, the per-GPU shape of configs[3] = the bs=8 step, configs[4] =
-        # generator_A2B bf16 inference at 16 x 512 frames.  The headline line above them is unchanged (configs[1], bs=1).
-        if world == 1 and B == 1 and T == 64 and not args.no_extra_configs and not args.serial:
+        # The --full single-GPU invocation also measures the other BASELINE configs, each as a nested record with its own roofline and CPU
+        # sample: configs[2] = the bs=32 step, the per-GPU shape of configs[3] = the bs=8 step, configs[4] = generator_A2B bf16 inference
+        # at 16 x 512 frames.  The headline line above them is unchanged (configs[1], bs=1).
+        extras = args.full and world == 1 and B == 1 and T == 64 and not args.no_extra_configs
+        if extras and not args.serial:
             extra = []
-            sub = argparse.Namespace(**dict(vars(args), dump_trace=None))
+            sub = argparse.Namespace(**dict(vars(args), dump_trace=None, dump_outputs=None))
             skip_cpu = args.cpu_iters == 0
             extra.append(train_record(sub, rank, world, device, 32, 64, 8, 3, 0 if skip_cpu else 1, 8, cpu_warm=False,
                                       config_id="configs[2]: bs=32, 1 GPU"))
             extra.append(train_record(sub, rank, world, device, 8, 64, 20, 5, 0 if skip_cpu else 2, 16, cpu_warm=False,
                                       config_id="configs[3] per-GPU shape: bs=8 (the 8-GPU run itself is the driver's)"))
             sub_i = argparse.Namespace(**dict(vars(sub), cpu_iters=0 if skip_cpu else -1))
-            rec = infer_record(sub_i, rank, world, device, "bf16", 16, 512, 30, 5)
+            cid = "configs[4]: generator_A2B inference, bs=16 x 512 frames, bf16"
+            rec = infer_record(sub_i, rank, world, device, "bf16", 16, 512, 30, 5, config_id=cid)
             if rec is not None:
-                rec["config_id"] = "configs[4]: generator_A2B inference, bs=16 x 512 frames, bf16"
+                rec["config_id"] = cid
             extra.append(rec)
             if res is not None:
                 res["configs"] = [r for r in extra if r is not None]
         # the price of the reference-exact loss readback, driver-observed: the same config once more, short, with
         # the CURRENT iteration's losses read every step
-        if world == 1 and B == 1 and T == 64 and not args.no_extra_configs and not (args.serial or args.sync_losses):
-            sub = argparse.Namespace(**dict(vars(args), dump_trace=None, no_trace=True, sync_losses=True))
+        if extras and not (args.serial or args.sync_losses):
+            sub = argparse.Namespace(**dict(vars(args), dump_trace=None, dump_outputs=None, no_trace=True, sync_losses=True))
             rec = train_record(sub, rank, world, device, 1, 64, 30, 5, 0, 16, config_id="sync-losses")
             if res is not None and rec is not None:
                 res["schedule"]["sync_losses_ms_per_step"] = rec["ms_per_step"]
@@ -546,7 +639,7 @@ def main():
             # ... and the regime a canonical run (bash_scripts/mask_cyclegan_train.sh: identity loss until 1e4 samples of ~5e5) spends > 97 % of
             # its iterations in: identity_loss_lambda = 0 (train.py:314-315), where the identity passes weigh nothing and are not computed.
             # The HEADLINE above stays the more expensive regime before the cut-off (lambda = 5): this is a second, labelled number.
-            sub = argparse.Namespace(**dict(vars(args), dump_trace=None, no_trace=True))
+            sub = argparse.Namespace(**dict(vars(args), dump_trace=None, dump_outputs=None, no_trace=True))
             rec = train_record(sub, rank, world, device, 1, 64, 40, 8, 0, 16, config_id="post-cutoff", stop_identity_after=0)
             if res is not None and rec is not None:
                 res["after_identity_cutoff"] = {"ms_per_step": rec["ms_per_step"], "iters_per_s": rec["value"], "identity_loss_lambda": rec["identity_loss_lambda"],

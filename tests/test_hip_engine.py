@@ -201,6 +201,19 @@ def _kink_free_batch(onets, B, T=64):
     raise AssertionError("no kink-free batch found")
 
 
+def _disc_output_bias_grads_fp64(onets, before, batch):
+    """The four discriminators' one-element output-bias gradients of the discriminator phase, evaluated in float64 from the same
+    float32 operands the HIP phase gets (the oracle's updated generators, the discriminators before their update, the batch).  Such a
+    gradient is (mean(D(real)) - 1 + mean(D(fake))) / 2: terms of ~0.5 that can cancel to ~1e-6, where the reference's own fp32
+    arithmetic sits a few 1e-2 from the exact value (measured: 2.0e-2 on discriminator_B2 at bs=32, at 3 and 8 host threads alike)."""
+    n64 = {n: {k: (onets[n][k] if n in G_NAMES else before[n][k]).double() for k in onets[n]} for n in orc.NET_ORDER}
+    bias = [n64[n]["outputConvLayer.0.bias"] for n in D_NAMES]
+    for t in bias:
+        t.requires_grad_(True)
+    d_loss = orc.StepOracle(n64).losses_d(*[b.double() for b in batch])
+    return dict(zip(D_NAMES, torch.autograd.grad(d_loss, bias)))
+
+
 @pytest.mark.parametrize("B,T,lam_id", [(1, 64, 5.0), (2, 64, 5.0), (1, 32, 5.0), (3, 48, 5.0), (8, 64, 5.0), (32, 64, 5.0), (1, 64, 0.0), (8, 64, 0.0)])
 def test_step_full_tensor_parity_vs_oracle(golden_dir, B, T, lam_id):
     """One iteration: every generator / discriminator parameter GRADIENT (full tensors) and the resulting Adam update
@@ -254,6 +267,7 @@ def test_step_full_tensor_parity_vs_oracle(golden_dir, B, T, lam_id):
             eu = float(((upd - upd_ref) * sig).norm() / max(float((upd_ref * sig).norm()), 1e-30))
             worst_u = max(worst_u, eu)
             assert eu < 2e-2, (name, k, eu)
+    bias64 = _disc_output_bias_grads_fp64(onets, before, batch)
     di = iter(d_grads)
     for name in D_NAMES:
         mod = dict(nets[name].named_parameters())
@@ -261,13 +275,20 @@ def test_step_full_tensor_parity_vs_oracle(golden_dir, B, T, lam_id):
             gr = next(di)
             if gr is None or float(gr.abs().max()) < 1e-6:
                 continue
-            e = float((mod[k].grad.detach().cpu().double() - gr.double()).norm() / gr.double().norm())
-            # single-element gradients (the 1-channel output bias) are sums of opposite-signed real/fake terms:
-            # cancellation amplifies rounding, so they get a looser bound
-            tol = 1e-2 if gr.numel() == 1 else 1e-3
-            if gr.numel() > 1:
-                worst_g = max(worst_g, e)
-            assert e < tol, (name, k, e)
+            mine = mod[k].grad.detach().cpu().double()
+            if gr.numel() == 1:
+                # single-element gradients (the 1-channel output bias) are sums of opposite-signed real/fake terms: cancellation
+                # amplifies rounding, so they get a looser bound, 1e-2 of the float64 value -- or, where the reference's fp32
+                # arithmetic is itself further off than that, "as accurate as the reference" (1.5x its distance, as in
+                # tests/test_hip_parity_fp64.py)
+                g64 = bias64[name].double()
+                e = float((mine - g64).norm() / g64.norm())
+                e_ref = float((gr.double() - g64).norm() / g64.norm())
+                assert e < max(1e-2, 1.5 * e_ref), (name, k, e, e_ref)
+                continue
+            e = float((mine - gr.double()).norm() / gr.double().norm())
+            worst_g = max(worst_g, e)
+            assert e < 1e-3, (name, k, e)
     print("B=%d worst gradient rel-L2 %.3e, worst significant-update rel-L2 %.3e" % (B, worst_g, worst_u))
 
 

@@ -35,8 +35,8 @@ json.dump(j, open('$OUT/pmc_traffic_bs$B.json','w'), indent=1)" && rm -f $OUT/pm
   DBA=$(pmc a $SQA -- $CMD); DBB=$(pmc b $SQB -- $CMD)
   { echo "# SQ counters per kernel (averages per dispatch), bs=$B, serial schedule, rev $REV"; echo "# pass A: $SQA"; python tools/rocpd_pmc.py $DBA; echo "# pass B: $SQB"; python tools/rocpd_pmc.py $DBB; } > $OUT/sq_bs$B.txt 2>&1
   python tools/sq_summary.py $DBA $DBB > $OUT/sq_summary_bs$B.txt 2>&1
-  if [ $B -eq 1 ]; then timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; fi
-  timeout 900 python bench.py --no-extra-configs --batch-size $B $CI > $OUT/bench_bs$B.json 2> $OUT/bench_bs$B.err
+  if [ $B -eq 1 ]; then timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; fi
+  timeout 900 python bench.py --full --no-extra-configs --batch-size $B $CI > $OUT/bench_bs$B.json 2> $OUT/bench_bs$B.err
   timeout 600 python bench.py --no-extra-configs --batch-size $B --cpu-iters 0 --steps $ST --warmup 4 --dump-trace $OUT/per_launch_trace_bs$B.txt > /dev/null 2>&1
   for MODE in serial concurrent; do
     F=""; if [ $MODE = serial ]; then F="--serial"; fi
@@ -51,8 +51,8 @@ if [ -n "$INFER" ]; then
   ICMD="python bench.py --mode infer --dtype bf16 --cpu-iters 0 --steps 10 --warmup 3"
   DBA=$(pmc ia $SQA -- $ICMD); DBB=$(pmc ib $SQB -- $ICMD)
   python tools/sq_summary.py $DBA $DBB > $OUT/sq_summary_infer_bf16.txt 2>&1
-  timeout 600 python bench.py --mode infer --dtype bf16 > $OUT/bench_infer_bf16.json 2> $OUT/bench_infer_bf16.err
-  timeout 600 python bench.py --mode infer --dtype f32 > $OUT/bench_infer_f32.json 2> $OUT/bench_infer_f32.err
+  timeout 600 python bench.py --full --mode infer --dtype bf16 > $OUT/bench_infer_bf16.json 2> $OUT/bench_infer_bf16.err
+  timeout 600 python bench.py --full --mode infer --dtype f32 > $OUT/bench_infer_f32.json 2> $OUT/bench_infer_f32.err
   rm -rf /tmp/prof_i; timeout 600 rocprofv3 --kernel-trace -d /tmp/prof_i -o x -- $ICMD > /dev/null 2>&1
   python tools/rocpd_stats.py $(find /tmp/prof_i -name "*.db" | head -1) 10 > $OUT/kernel_stats_infer_bf16.txt 2>&1
 fi
