@@ -114,7 +114,10 @@ int mcvc_disc_pack_small(const float* const* params, float* packed, int T, void*
 int mcvc_disc_pack_batch(const float* const* params, float* packed, int max_batch, int T, void* stream);
 
 /* ---- Generator: replaces Generator.forward (mask_cyclegan_vc/model.py:239-280) and its autograd
- *      x, mask: [B,80,T] (mask NULL = all ones, test.py:92); out: [B,80,T']                        */
+ *      x, mask: [B,80,T] (mask NULL = all ones, test.py:92); out: [B,80,T']
+ *      T >= 5: at T <= 4 the residual trunk runs on a single frame, where the reference's InstanceNorm1d raises
+ *      ("Expected more than 1 spatial element"); every generator pass (forward, backward, bf16 inference) then
+ *      returns MCVC_ERR_INVALID.                                                                    */
 int mcvc_gen_forward(const float* const* params, const float* packed, const float* x, const float* mask,
                      float* out, float* stash, float* scratch, long long scratch_floats, int B, int T, void* stream);
 /*      dout: [B,80,T'] ; dx (nullable): [B,80,T], written or accumulated (accumulate_dx != 0)      */

@@ -302,7 +302,7 @@ int mcvc_gen_infer_bf16(const float* const* params, const void* packed, const fl
 {
     if (B < 1 || T < 1 || !params || !packed || !x || !out || !workspace) return MCVC_ERR_INVALID;
     const Dims d = dims(B, T);
-    if (d.W4 < 1) return MCVC_ERR_INVALID;
+    if (d.W4 < 2) return MCVC_ERR_INVALID;        // T <= 4: the trunk's InstanceNorm1d would see one frame (the reference raises there too)
     const Work w = work(d);
     if (workspace_bytes < w.bytes) return MCVC_ERR_WORKSPACE;
     if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(packed)) & 15) return MCVC_ERR_INVALID;

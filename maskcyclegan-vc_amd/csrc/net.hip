@@ -2527,6 +2527,7 @@ int mcvc_gen_forward(const float* const* params, const float* packed, const floa
 {
     if (B < 1 || T < 1 || !params || !packed || !x || !out || !stash || !scratch) return MCVC_ERR_INVALID;
     const GenDims d = gen_dims(B, T);
+    if (d.W4 < 2) return MCVC_ERR_INVALID;        // T <= 4: the trunk's InstanceNorm1d would see one frame (the reference raises there too)
     Exec ex = make_exec(stream, nullptr, scratch, scratch_floats, gen_scratch(d).slabs, gen_needs(B, T));
     if (ex.wslab_cap < 0) return MCVC_ERR_WORKSPACE;
     { const GenScratch q = gen_scratch(d); ex.wv = scratch + q.wv; ex.wm = scratch + q.wm; ex.wino_cap = q.wino_floats;
@@ -2582,6 +2583,7 @@ int mcvc_gen_backward_window(const float* const* params, const float* packed, fl
 {
     if (B < 1 || T < 1 || stash_b0 < 0 || stash_B < stash_b0 + B || !params || !packed || !dout || !stash || !scratch) return MCVC_ERR_INVALID;
     const GenDims d = gen_dims(B, T);
+    if (d.W4 < 2) return MCVC_ERR_INVALID;        // (as mcvc_gen_forward)
     Exec ex = make_exec(stream, aux_stream, scratch, scratch_floats, gen_scratch(d).slabs, gen_needs(B, T));
     if (ex.wslab_cap < 0) return MCVC_ERR_WORKSPACE;
     { const GenScratch q = gen_scratch(d); ex.wv = scratch + q.wv; ex.wm = scratch + q.wm; ex.wino_cap = q.wino_floats;

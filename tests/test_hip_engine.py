@@ -214,7 +214,9 @@ def _disc_output_bias_grads_fp64(onets, before, batch):
     return dict(zip(D_NAMES, torch.autograd.grad(d_loss, bias)))
 
 
-@pytest.mark.parametrize("B,T,lam_id", [(1, 64, 5.0), (2, 64, 5.0), (1, 32, 5.0), (3, 48, 5.0), (8, 64, 5.0), (32, 64, 5.0), (1, 64, 0.0), (8, 64, 0.0)])
+@pytest.mark.parametrize("B,T,lam_id", [(1, 64, 5.0), (2, 64, 5.0), (1, 32, 5.0), (3, 48, 5.0), (8, 64, 5.0), (32, 64, 5.0), (1, 64, 0.0), (8, 64, 0.0),
+                                         # --num_frames other than 64: trunk, discriminator and last-layer weight-gradient paths differ
+                                         (1, 100, 5.0), (1, 128, 5.0), (2, 256, 5.0)])
 def test_step_full_tensor_parity_vs_oracle(golden_dir, B, T, lam_id):
     """One iteration: every generator / discriminator parameter GRADIENT (full tensors) and the resulting Adam update
     vs the CPU oracle.  (8, 64) is the per-GPU shape of BASELINE configs[3], (32, 64) is configs[2]: the staged-GEMM trunk

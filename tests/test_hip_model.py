@@ -90,7 +90,11 @@ def test_gradients_match_reference_goldens(golden_dir, meta, nets):
     assert checked > 80
 
 
-@pytest.mark.parametrize("B,T", [(1, 64), (3, 64), (2, 24), (1, 68), (4, 64), (6, 48)])
+@pytest.mark.parametrize("B,T", [(1, 64), (3, 64), (2, 24), (1, 68), (4, 64), (6, 48),
+                                 (1, 65), (1, 66),    # stride-2 data gradients on odd sizes, the generic InstanceNorm backward
+                                 (1, 100),            # W4 = 25 (odd); discriminator (W/2) & 3 != 0: no implicit GEMM
+                                 (1, 132), (2, 256),  # staged-GEMM trunk at small batch (past the fused trunk's W4 <= 32)
+                                 (1, 520)])           # discriminator first-layer weight gradient past wgrad_cin1's W <= 512
 def test_full_tensor_parity_vs_oracle(B, T, nets, meta):
     """Every parameter gradient and the input gradient, full tensors, vs the CPU oracle.  With T % 16 == 0, upSample2 (from 4 samples also
     upSample1) runs as F(4x4,5x5) Winograd (64 points, csrc/wino4.h) and from 4 samples downSample1/2 as F(4x4,3x3) over the phase

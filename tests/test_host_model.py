@@ -81,3 +81,26 @@ def test_block_constructors_match_reference_signatures():
     assert PixelShuffle(2)(torch.zeros(2, 8, 5)).shape == (2, 4, 10)
     with pytest.raises(ValueError):
         Generator(input_shape=(24, 64))
+
+
+def _co(w):
+    """Output width of the stride-2 convolutions of both networks (kernel 5 pad 2 in the generator, 3 pad 1 in the discriminator)."""
+    return (w - 1) // 2 + 1
+
+
+def test_output_frames_follow_the_reference_convolutions():
+    """mcvc_gen_out_frames / mcvc_disc_out_frames size every output buffer: the generator's is two stride-2 convolutions followed by
+    two 2x pixel shuffles (reference model.py:245-275), the discriminator's three stride-2 convolutions (model.py:345-347).  Checked
+    at every length from the smallest valid one to beyond the longest utterances, and for a dozen lengths against the widths the
+    oracle's own convolutions produce."""
+    import mcvc_oracle as orc
+    L = _hip.lib()
+    bad = [(T, L.mcvc_gen_out_frames(T), L.mcvc_disc_out_frames(T)) for T in range(5, 2101)
+           if L.mcvc_gen_out_frames(T) != 4 * _co(_co(T)) or L.mcvc_disc_out_frames(T) != _co(_co(_co(T)))]
+    assert not bad, bad[:8]
+    gp, dp = orc.filler_params("G", 1), orc.filler_params("D", 2)
+    with torch.no_grad():
+        for T in (5, 6, 7, 8, 13, 31, 33, 63, 65, 66, 67, 100):
+            x = torch.randn(1, 80, T, generator=torch.Generator().manual_seed(T))
+            assert orc.generator_forward(gp, x, torch.ones_like(x)).shape == (1, 80, L.mcvc_gen_out_frames(T)), T
+            assert orc.discriminator_forward(dp, x).shape == (1, 1, 10, L.mcvc_disc_out_frames(T)), T
