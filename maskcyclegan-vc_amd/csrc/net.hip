@@ -869,8 +869,11 @@ static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, int NB,
     if (implicit) {
         const int tiles = (c.cout_tot / 128) * (c.Cin / mcvc_wgemm_cib(wtaps));
         const long long nst = ((long long)NB * OH * OW + 31) / 32;
-        static const int wg_target = mcvc_knob("MCVC_WGEMM_WGS", 256), wg_max = mcvc_knob("MCVC_WGEMM_MAXSPLIT", 64);
-        // (a workgroup per compute unit -- a tile holds 156 KB of LDS -- and at least two pixel stages per split)
+        static const int wg_target = mcvc_knob("MCVC_WGEMM_WGS", 128), wg_max = mcvc_knob("MCVC_WGEMM_MAXSPLIT", 64);
+        // (a workgroup per compute unit -- a tile holds 156 KB of LDS -- and at least two pixel stages per split.  The target is 128 per
+        // NETWORK: a grouped pass (twin.h) launches both networks' tiles in one grid, and at 256 per network that grid ran two rounds on
+        // 256 CUs while dw_accum summed twice the slabs -- bs=1 step 5.70 -> 5.60 ms at 128.  The ungrouped passes plan the same split,
+        // so the grouped step stays bit-identical to the four-lane one.)
         while (wg_split < wg_max && tiles * wg_split < wg_target && nst / (2 * wg_split) >= 2) wg_split *= 2;
         sg_floats = wg_split > 1 ? (long long)wg_split * c.cout_tot * KT : 0;
     }
