@@ -295,6 +295,31 @@ int mcvc_draw_batch(const float* bank_A, const int* offs_A, int n_A, long long f
                     long long frames_B, int B, int T, int max_mask_len, unsigned long long seed, unsigned long long step,
                     float* real_A, float* mask_A, float* real_B, float* mask_B, int* draws, void* stream);
 
+/* ---- waveform -> log-mel front-end (new: the reference computes its mel-spectrograms with the MelGAN vocoder's Audio2Mel module,
+ *      fetched through torch.hub -- data_preprocessing/preprocess_vcc2018.py:26-60, mask_cyclegan_vc/utils.py).  The fixed transform
+ *      Audio2Mel(n_fft 1024, hop 256, win 1024, 22050 Hz, 80 mel rows, fmin 0, fmax 11025) of a mono float waveform of L samples:
+ *      reflect-pad 384 each side, T = (L - 256) / 256 + 1 frames of 1024 at hop 256, periodic Hann, |DFT| of bins 0..512, the
+ *      [80][513] Slaney mel filterbank, log10(max(., 1e-5)).  L < 385 is refused (reflect padding needs L > 384).
+ *      A BANK is n utterances concatenated in one fp32 buffer + int32 sample offsets [n + 1] (the layout of mcvc_draw_batch's banks);
+ *      one launch turns it into out [80][total_frames], utterance u in columns frame_offs[u] .. frame_offs[u + 1].
+ *        mcvc_audio_frames       frames of an L-sample utterance; 0 when L < 385.
+ *        mcvc_audio_basis_floats size of the constant operand: the windowed cos / sin DFT basis in the order the kernel's lanes read it,
+ *                                followed by the sparse mel table.
+ *        mcvc_audio_basis_init   fills it, computed in float64 and rounded once.  `basis` is a HOST buffer; the caller uploads it
+ *                                (16-byte aligned) and keeps it: it never changes.
+ *        mcvc_audio_plan         HOST tables in, HOST tables out: frame_offs [n + 1] and the launch's work list tiles [n_tiles][4] int32
+ *                                (at most 64 frames of one utterance each).  tiles == NULL: only *n_tiles and frame_offs are written.
+ *                                MCVC_ERR_INVALID: n < 1, an utterance under 385 samples, >= 2^31 frames; MCVC_ERR_WORKSPACE: max_tiles
+ *                                too small.
+ *        mcvc_audio_log_mel      the launch: wave, tiles (16-byte aligned), basis, out are DEVICE pointers.  A work item that does not
+ *                                lie inside [0, n_samples) x [0, total_frames) is skipped, never followed out of bounds.            */
+int mcvc_audio_frames(int n_samples);
+long long mcvc_audio_basis_floats(void);
+int mcvc_audio_basis_init(float* basis);
+int mcvc_audio_plan(const int* sample_offs, int n_utts, int* frame_offs, int* tiles, int max_tiles, int* n_tiles);
+int mcvc_audio_log_mel(const float* wave, long long n_samples, const int* tiles, int n_tiles, const float* basis, float* out,
+                       long long total_frames, void* stream);
+
 /* ---- single-op entry points (kernel parity tests; same kernels the network calls use) ---------- */
 /* y[N,Cout,OH,OW] = conv2d(x[N,Cin,H,W], w[Cout,Cin,KH,KW]) + bias ; stride 1 or 2.
  * wpack: scratch of mcvc_conv2d_pack_floats() floats, zero-initialised by the caller.

@@ -13,5 +13,8 @@ class CycleGANTestArgParser(BaseArgParser):
         ("--model_name", dict(type=str, choices=("generator_A2B", "generator_B2A"), default="generator_A2B", help="Name of model to load.")),
         # (new) MI355X inference knobs -- additive, defaults reproduce the reference's fp32 one-utterance-at-a-time results
         ("--dtype", dict(type=str, choices=("f32", "bf16"), default="f32", help="(new) arithmetic of the generator forward: f32 (reference numerics) or bf16 MFMA.")),
+        ("--wav_dir", dict(type=str, default=None, help="(new) convert the .wav files of this folder (sorted, recursive) instead of the source speaker's "
+                           "preprocessed utterances: mels come from the GPU front-end (data_preprocessing/audio2mel.py) and are standardised with the source "
+                           "speaker's norm_stat.npz.  Files not at 22050 Hz are resampled with scipy.signal.resample_poly, which is not librosa's resampler.")),
         ("--max_batch", dict(type=int, default=16, help="(new) utterances of identical length are converted in one batched forward of up to this many.")),
     ]

@@ -22,6 +22,7 @@
 #include "wino4.h"
 #include "sgemm.h"
 #include "sampler.h"
+#include "audio.h"
 #include "../../include/mcvc.h"
 #include <string.h>
 #include <algorithm>
@@ -2674,6 +2675,28 @@ int mcvc_draw_batch(const float* bank_A, const int* offs_A, int n_A, long long f
     a.n[0] = n_A; a.n[1] = n_B; a.B = B; a.T = T; a.max_mask_len = max_mask_len; a.seed = seed; a.step = step;
     a.real[0] = real_A; a.real[1] = real_B; a.mask[0] = mask_A; a.mask[1] = mask_B; a.draws = draws;
     return mcvc_draw_batch_launch(a, (hipStream_t)stream);
+}
+
+int mcvc_audio_frames(int n_samples) { return mcvc_audio_frames_of(n_samples); }
+
+long long mcvc_audio_basis_floats(void) { return mcvc_audio_basis_floats_of(); }
+
+int mcvc_audio_basis_init(float* basis)
+{
+    if (!basis || ((uintptr_t)basis & 3)) return MCVC_ERR_INVALID;
+    mcvc_audio_basis_fill(basis);
+    return MCVC_OK;
+}
+
+int mcvc_audio_plan(const int* sample_offs, int n_utts, int* frame_offs, int* tiles, int max_tiles, int* n_tiles)
+{
+    return mcvc_audio_plan_host(sample_offs, n_utts, frame_offs, tiles, max_tiles, n_tiles);
+}
+
+int mcvc_audio_log_mel(const float* wave, long long n_samples, const int* tiles, int n_tiles, const float* basis, float* out,
+                       long long total_frames, void* stream)
+{
+    return mcvc_audio_log_mel_launch(wave, n_samples, tiles, n_tiles, basis, out, total_frames, (hipStream_t)stream);
 }
 
 int mcvc_axpy(float* y, const float* x, float alpha, long long n, void* stream)

@@ -1,0 +1,206 @@
+"""Waveform -> log-mel front-end on the GPU: the MelGAN vocoder's ``Audio2Mel`` transform, which the reference obtains through
+``torch.hub`` (data_preprocessing/preprocess_vcc2018.py:26-60, mask_cyclegan_vc/utils.py) and this project restates from its
+published definition -- no network access, no trained weights, no librosa / torchaudio.
+
+``Audio2Mel(n_fft=1024, hop_length=256, win_length=1024, sampling_rate=22050, n_mel_channels=80, mel_fmin=0.0, mel_fmax=None)``
+on one mono float waveform of L samples:
+
+1. reflect-pad (1024 - 256) / 2 = 384 samples each side (``F.pad(..., 'reflect')``: the edge sample is not repeated; L >= 385);
+2. T = (L - 256) // 256 + 1 frames, frame t = padded samples [256 t, 256 t + 1024) (``center=False``);
+3. periodic Hann window of 1024, DFT, bins 0..512, magnitude sqrt(re^2 + im^2);
+4. mel = B @ magnitude with the [80, 513] Slaney filterbank of ``mel_filterbank`` (what ``librosa.filters.mel(sr=22050, n_fft=1024,
+   n_mels=80, fmin=0, fmax=11025, htk=False, norm='slaney')`` is defined to return);
+5. log10(clamp(mel, min=1e-5)), float32 [80, T].
+
+Steps 1-5 are ONE HIP launch for a whole bank of utterances (csrc/audio_kernels.hip through ``mcvc_audio_log_mel``): a speaker's
+recordings are concatenated in one buffer with an offset table and come back as one [80, total_frames] matrix.  There is no CPU path.
+
+``read_wav`` follows ``librosa.load(path, sr=22050, mono=True)``: integer PCM scaled by 1 / 2^(bits-1), channels averaged; a file at
+another rate is resampled on the host with ``scipy.signal.resample_poly`` -- NOT librosa's resampler (soxr / resampy), so such files
+give close but not identical samples.  VCC2018 is recorded at 22050 Hz and never takes that branch.
+"""
+import ctypes
+from math import gcd
+
+import numpy as np
+
+SAMPLING_RATE = 22050
+N_FFT = 1024
+HOP_LENGTH = 256
+N_MEL = 80
+MIN_SAMPLES = (N_FFT - HOP_LENGTH) // 2 + 1        # reflect padding of 384 needs at least 385 samples
+
+
+def num_frames(n_samples):
+    """Frames of an utterance of ``n_samples`` samples; raises below 385 samples like torch's reflect padding."""
+    n_samples = int(n_samples)
+    if n_samples < MIN_SAMPLES:
+        raise ValueError("Audio2Mel needs at least %d samples (reflect padding of %d), got %d" % (MIN_SAMPLES, MIN_SAMPLES - 1, n_samples))
+    return (n_samples - HOP_LENGTH) // HOP_LENGTH + 1
+
+
+def _hz_to_mel(f):
+    f = np.asarray(f, dtype=np.float64)
+    return np.where(f >= 1000.0, 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) / (np.log(6.4) / 27.0), f / (200.0 / 3.0))
+
+
+def _mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (m - 15.0)), (200.0 / 3.0) * m)
+
+
+def mel_filterbank(dtype=np.float32):
+    """The [80, 513] Slaney mel basis (triangles between 82 band edges equally spaced on the Slaney mel scale from 0 to 11025 Hz,
+    each scaled by 2 / its width in Hz), built in float64 and returned as ``dtype``."""
+    fmax = SAMPLING_RATE / 2.0
+    f = np.linspace(0.0, fmax, N_FFT // 2 + 1)
+    e = _mel_to_hz(np.linspace(_hz_to_mel(0.0), _hz_to_mel(fmax), N_MEL + 2))
+    up = (f[None, :] - e[:-2, None]) / (e[1:-1] - e[:-2])[:, None]
+    down = (e[2:, None] - f[None, :]) / (e[2:] - e[1:-1])[:, None]
+    basis = np.maximum(0.0, np.minimum(up, down)) * (2.0 / (e[2:] - e[:-2]))[:, None]
+    return basis.astype(dtype)
+
+
+def _to_float(data):
+    if data.dtype.kind == "f":
+        return data.astype(np.float32)
+    if data.dtype == np.uint8:                                         # 8-bit PCM is unsigned, centred on 128
+        return (data.astype(np.float32) - 128.0) / 128.0
+    if data.dtype.kind == "i":
+        return (data.astype(np.float64) / float(1 << (8 * data.dtype.itemsize - 1))).astype(np.float32)
+    raise ValueError("unsupported sample type %s" % data.dtype)
+
+
+def _read_with_wave_module(path):
+    import wave
+    try:
+        with wave.open(path, "rb") as fh:                              # the stdlib reader knows uncompressed PCM only
+            rate, width, ch, n = fh.getframerate(), fh.getsampwidth(), fh.getnchannels(), fh.getnframes()
+            raw = fh.readframes(n)
+    except (wave.Error, EOFError) as exc:
+        raise ValueError("%s: not a readable uncompressed PCM .wav file (%s)" % (path, exc))
+    if width == 3:
+        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+        data = ((b[:, 0] << 8) | (b[:, 1] << 16) | (b[:, 2] << 24)).astype(np.int32)
+    elif width in (1, 2, 4):
+        data = np.frombuffer(raw, dtype={1: np.uint8, 2: "<i2", 4: "<i4"}[width])
+    else:
+        raise ValueError("%s: unsupported sample width of %d bytes" % (path, width))
+    return rate, data.reshape(-1, ch) if ch > 1 else data
+
+
+def read_wav(path, sampling_rate=SAMPLING_RATE):
+    """-> float32 mono waveform at ``sampling_rate`` (22050 Hz), like ``librosa.load(path, sr=22050, mono=True)`` except for the
+    resampler (module docstring).  Raises ValueError for compressed, empty or unreadable files."""
+    path = str(path)
+    try:
+        from scipy.io import wavfile
+    except ImportError:
+        wavfile = None
+    if wavfile is not None:
+        import warnings
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")                        # (non-audio chunks in the header are not an error)
+                rate, data = wavfile.read(path)
+        except FileNotFoundError:
+            raise
+        except Exception as exc:                                       # scipy raises ValueError for formats it does not decode
+            raise ValueError("%s: not a readable uncompressed .wav file (%s)" % (path, exc))
+    else:
+        rate, data = _read_with_wave_module(path)
+    x = _to_float(np.asarray(data))
+    if x.ndim == 2:
+        x = x.mean(axis=1, dtype=np.float32)
+    if x.size == 0:
+        raise ValueError("%s: no samples" % path)
+    if int(rate) != int(sampling_rate):
+        from scipy.signal import resample_poly
+        g = gcd(int(sampling_rate), int(rate))
+        x = resample_poly(x.astype(np.float64), int(sampling_rate) // g, int(rate) // g)
+    return np.ascontiguousarray(x, dtype=np.float32)
+
+
+class Audio2Mel(object):
+    """The vocoder's front-end as a callable: ``fft(x)`` with ``x`` a HIP-device tensor [B, 1, L] or [B, L] -> [B, 80, T]
+    (the convention of the reference's ``vocoder.fft``), and ``fft.bank(waveforms)`` for utterances of different lengths:
+    one launch, one float32 [80, T_i] array per utterance."""
+
+    _basis = {}                                                        # device index -> the constant operand, uploaded once
+
+    def __init__(self, device=None):
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("data_preprocessing.audio2mel (MI355X build) needs a HIP device; there is no CPU path")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("data_preprocessing.audio2mel (MI355X build): device must be a HIP device; there is no CPU path")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+
+    def basis(self):
+        import torch
+        from mask_cyclegan_vc._hip import check, lib
+        t = Audio2Mel._basis.get(self.device.index)
+        if t is None:
+            L = lib()
+            host = np.empty(L.mcvc_audio_basis_floats(), dtype=np.float32)
+            check(L.mcvc_audio_basis_init(host.ctypes.data), "mcvc_audio_basis_init")
+            t = Audio2Mel._basis[self.device.index] = torch.from_numpy(host).to(self.device)
+        return t
+
+    def _launch(self, wave, lengths):
+        """wave: contiguous float32 device tensor holding the utterances back to back -> ([80, total_frames] device tensor, frame offsets)."""
+        import torch
+        from mask_cyclegan_vc._hip import check, lib, ptr, stream
+        L = lib()
+        n = len(lengths)
+        offs = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.asarray(lengths, dtype=np.int64), out=offs[1:])
+        if n < 1 or offs[-1] >= 2 ** 31:
+            raise ValueError("a bank holds between 1 utterance and 2^31 - 1 samples")
+        for k in lengths:
+            num_frames(k)                                              # raises for an utterance under 385 samples
+        offs = offs.astype(np.int32)
+        frame_offs = np.zeros(n + 1, dtype=np.int32)
+        n_tiles = ctypes.c_int(0)
+        check(L.mcvc_audio_plan(offs.ctypes.data, n, frame_offs.ctypes.data, None, 0, ctypes.byref(n_tiles)), "mcvc_audio_plan")
+        tiles = np.zeros((n_tiles.value, 4), dtype=np.int32)
+        check(L.mcvc_audio_plan(offs.ctypes.data, n, frame_offs.ctypes.data, tiles.ctypes.data, n_tiles.value, ctypes.byref(n_tiles)), "mcvc_audio_plan")
+        total = int(frame_offs[-1])
+        with torch.cuda.device(self.device):
+            tiles_d = torch.from_numpy(tiles).to(self.device)
+            out = torch.empty(N_MEL, total, dtype=torch.float32, device=self.device)
+            check(L.mcvc_audio_log_mel(ptr(wave), int(offs[-1]), ptr(tiles_d), n_tiles.value, ptr(self.basis()), ptr(out), total, stream()),
+                  "mcvc_audio_log_mel")
+        return out, frame_offs
+
+    def bank(self, waveforms):
+        """list of 1-D waveforms (numpy or tensors, any float type) -> list of float32 numpy [80, T_i], from a single launch."""
+        import torch
+        ws = [np.ascontiguousarray(w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else w, dtype=np.float32).reshape(-1) for w in waveforms]
+        if not ws:
+            return []
+        lengths = [w.size for w in ws]
+        for k in lengths:
+            num_frames(k)
+        wave = torch.from_numpy(np.concatenate(ws)).to(self.device)
+        out, fo = self._launch(wave, lengths)
+        host = out.cpu().numpy()
+        return [np.ascontiguousarray(host[:, fo[i]:fo[i + 1]]) for i in range(len(ws))]
+
+    def __call__(self, x):
+        import torch
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError("data_preprocessing.audio2mel (MI355X build): tensors must live on a HIP device; there is no CPU path")
+        if x.dim() == 3 and x.shape[1] == 1:
+            x = x[:, 0]
+        if x.dim() != 2:
+            raise ValueError("expected a [B, 1, L] or [B, L] waveform tensor, got %s" % (tuple(x.shape),))
+        B, n = x.shape
+        T = num_frames(n)
+        if x.device != self.device:
+            raise RuntimeError("waveform on %s, front-end on %s" % (x.device, self.device))
+        wave = x.to(torch.float32).contiguous()
+        out, _ = self._launch(wave, [n] * B)
+        return out.view(N_MEL, B, T).permute(1, 0, 2).contiguous()

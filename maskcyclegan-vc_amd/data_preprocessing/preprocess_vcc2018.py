@@ -1,17 +1,20 @@
 """Writer of the preprocessed-dataset format the trainer reads (reference data_preprocessing/preprocess_vcc2018.py:26-85).
 
 The reference turns ``.wav`` files into 80-bin mel-spectrograms with the MelGAN vocoder's front-end (``torch.hub``
-descriptinc/melgan-neurips + librosa: network and audio packages, out of scope here -- SURVEY.md section 2 row 9), then
-standardises per bin over the whole speaker and writes two files.  This module owns everything AFTER the wav -> mel step,
-so mel-spectrograms produced by any front-end (``.npy`` files, one ``[80, T]`` array per utterance) become a dataset that
-both this trainer and the reference trainer load:
+descriptinc/melgan-neurips + librosa), then standardises per bin over the whole speaker and writes two files:
 
     <cache>/<spk>/<spk>_normalized.pickle   list of float32 [80, T_i], (mel - mean) / std          (:40-47, :83)
     <cache>/<spk>/<spk>_norm_stat.npz       mean, std: [80, 1]; std = np.std(...) + 1e-9          (:36-38, :78-80)
 
-Utterances shorter than 64 frames are dropped like the reference does (:33).
+Utterances shorter than 64 frames are dropped like the reference does (:33).  Two inputs are accepted, exactly one per run:
 
-    python -m data_preprocessing.preprocess_vcc2018 --mel_directory mels/ --preprocessed_data_directory out/ --speaker_ids A B
+    --data_directory <dir>   the reference's flag: <dir>/<speaker_id>/**/*.wav.  The wav -> mel step is this project's GPU front-end
+                             (data_preprocessing/audio2mel.py: the same fixed transform, one launch per speaker, needs a HIP device).
+                             Files that are not at 22050 Hz are resampled with scipy.signal.resample_poly, which is not librosa's
+                             resampler; VCC2018 is at 22050 Hz.
+    --mel_directory <dir>    <dir>/<speaker_id>/**/*.npy, one [80, T] mel-spectrogram per utterance from any front-end.
+
+    python -m data_preprocessing.preprocess_vcc2018 --data_directory vcc2018/vcc2018_training --preprocessed_data_directory out/ --speaker_ids A B
 """
 import argparse
 import glob
@@ -45,15 +48,41 @@ def save_preprocessed(cache_folder, speaker_id, mel_list):
     return d
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(description="mel-spectrogram .npy files -> preprocessed speaker folders")
-    ap.add_argument("--mel_directory", type=str, required=True, help="<dir>/<speaker_id>/**/*.npy, one [80,T] array per utterance")
+def speaker_mels_from_wavs(data_directory, speaker_id, fft=None):
+    """Sorted <dir>/<spk>/**/*.wav -> (files, list of float32 [80, T_i]): one bank launch for the whole speaker."""
+    from .audio2mel import Audio2Mel, read_wav
+    files = sorted(glob.glob(os.path.join(data_directory, speaker_id, "**", "*.wav"), recursive=True))
+    if not files:
+        raise ValueError("no .wav files under %s" % os.path.join(data_directory, speaker_id))
+    fft = fft or Audio2Mel()
+    return files, fft.bank([read_wav(f) for f in files])
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description=".wav files (or mel-spectrogram .npy files) -> preprocessed speaker folders")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--data_directory", type=str, default=None,
+                     help="<dir>/<speaker_id>/**/*.wav (the reference's flag); mels are computed on the GPU.  Files not at 22050 Hz are "
+                          "resampled with scipy.signal.resample_poly, which is not librosa's resampler.")
+    src.add_argument("--mel_directory", type=str, default=None, help="<dir>/<speaker_id>/**/*.npy, one [80,T] array per utterance")
     ap.add_argument("--preprocessed_data_directory", type=str, default="vcc2018_preprocessed/vcc2018_training")
     ap.add_argument("--speaker_ids", nargs="+", type=str, required=True)
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    fft = None
     for spk in args.speaker_ids:
-        files = sorted(glob.glob(os.path.join(args.mel_directory, spk, "**", "*.npy"), recursive=True))
-        d = save_preprocessed(args.preprocessed_data_directory, spk, [np.load(f) for f in files])
+        if args.data_directory is not None:
+            if fft is None:
+                from .audio2mel import Audio2Mel
+                fft = Audio2Mel()
+            files, mels = speaker_mels_from_wavs(args.data_directory, spk, fft)
+        else:
+            files = sorted(glob.glob(os.path.join(args.mel_directory, spk, "**", "*.npy"), recursive=True))
+            mels = [np.load(f) for f in files]
+        d = save_preprocessed(args.preprocessed_data_directory, spk, mels)
         print("Preprocessed and saved data for speaker: %s (%d files) -> %s" % (spk, len(files), d))
 
 

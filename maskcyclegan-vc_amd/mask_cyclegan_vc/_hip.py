@@ -94,6 +94,11 @@ _SIGS = {
                                        c_float, c_float, c_float, c_float, c_int, c_float, c_int, c_void_p]),
     "mcvc_draw_batch": (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_int, c_longlong, c_int, c_int, c_int,
                                 ctypes.c_ulonglong, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mcvc_audio_frames": (c_int, [c_int]),
+    "mcvc_audio_basis_floats": (c_longlong, []),
+    "mcvc_audio_basis_init": (c_int, [c_void_p]),
+    "mcvc_audio_plan": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "mcvc_audio_log_mel": (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_longlong, c_void_p]),
     "mcvc_axpy": (c_int, [c_void_p, c_void_p, c_float, c_longlong, c_void_p]),
     "mcvc_conv2d_pack_floats": (c_longlong, [c_int, c_int, c_int, c_int]),
     "mcvc_conv2d_forward": (c_int, [c_void_p] * 6 + [c_int] * 12 + [c_void_p]),

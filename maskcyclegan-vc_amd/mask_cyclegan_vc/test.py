@@ -8,7 +8,10 @@ Batching (new): InstanceNorm statistics run over an utterance's whole time axis,
 length would change every output.  Utterances are therefore bucketed by EXACT length: a bucket of k equal-length utterances
 is one batched forward (up to ``--max_batch``; every op is per-sample, so results equal the bs=1 results), buckets are
 visited longest first and alternate between two HIP streams so that short utterances overlap on the chip.  ``--dtype bf16``
-selects the bf16-MFMA forward (BASELINE configs[4])."""
+selects the bf16-MFMA forward (BASELINE configs[4]).
+
+``--wav_dir`` (new): the utterances to convert are the .wav files of a folder instead of the source speaker's pickle; their
+mel-spectrograms come from the GPU front-end (data_preprocessing/audio2mel.py)."""
 import os
 
 import numpy as np
@@ -38,9 +41,22 @@ class MaskCycleGANVCTesting(object):
         self.saver = ModelSaver(args)
         self.saver.load_model(self.generator, self.model_name)
 
+    def wav_dir_utterances(self, mean, std):
+        """--wav_dir: the folder's recordings (sorted) -> log-mels on the GPU (one launch) -> standardised with the SOURCE speaker's
+        statistics, as the reference standardises what it feeds the generator (test.py:88-90)."""
+        import glob
+        from data_preprocessing.audio2mel import Audio2Mel, read_wav
+        files = sorted(glob.glob(os.path.join(self.args.wav_dir, "**", "*.wav"), recursive=True))
+        if not files:
+            raise ValueError("no .wav files under %s" % self.args.wav_dir)
+        mels = Audio2Mel(self.device).bank([read_wav(f) for f in files])
+        return [((m - mean) / std).astype(np.float32) for m in mels]
+
     def test(self):
         a2b = self.model_name == "generator_A2B"
         src = self.dataset_A if a2b else self.dataset_B
+        if self.args.wav_dir:
+            src = self.wav_dir_utterances(*((self.dataset_A_mean, self.dataset_A_std) if a2b else (self.dataset_B_mean, self.dataset_B_std)))
         mean, std = (self.dataset_B_mean, self.dataset_B_std) if a2b else (self.dataset_A_mean, self.dataset_A_std)
         tag = ("%s_to_%s" % (self.args.speaker_A_id, self.args.speaker_B_id)) if a2b else ("%s_to_%s" % (self.args.speaker_B_id, self.args.speaker_A_id))
         outs = [None] * len(src)
