@@ -364,7 +364,8 @@ int mcvc_layer_wgrad(const float* x, const float* dy, float* dw0, float* dw1, fl
  *      autograd): InstanceNorm (+ gated GLU when the gate pointers are given) backward of dy [Cout][B][T4] recomputed inside the
  *      transposed-convolution launch; dconv [Cx][B][T4] = gradient w.r.t. the conv output (Cx = Cout or 2*Cout, value rows first);
  *      dx [Cin][B][T4] += data gradient; d(gamma), d(beta) += (nullable); x_in != NULL (k = 3): dw / dw_gate += weight gradients.
- *      wpack: Cin * Cx * KW floats of workspace (the transposed weight copy).                                                          */
+ *      wpack: Cin * Cx * KW floats of workspace (the transposed weight copy).  Deterministic mode: the K slices of the data gradient run as
+ *      launches one after the other, each adding to dx with plain stores (this entry has no slab workspace), instead of one launch with atomics. */
 int mcvc_trunk_layer_backward(const float* dy, const float* conv_out, const float* stats, const float* gamma, const float* beta,
                               const float* gamma_gate, const float* beta_gate, const float* w, const float* w_gate, const float* x_in,
                               float* dx, float* dconv, float* dgamma, float* dbeta, float* dgamma_gate, float* dbeta_gate, float* dw,

@@ -3025,7 +3025,10 @@ int mcvc_trunk_layer_backward(const float* dy, const float* conv_out, const floa
     a.pre = glu ? 2 : 1; a.pre_C = Cout; a.pre_x = conv_out; a.pre_stats = stats;
     a.pre_gamma0 = gamma; a.pre_beta0 = beta; a.pre_gamma1 = gamma_gate; a.pre_beta1 = beta_gate;
     a.pre_out = dconv; a.pre_dgamma0 = dgamma; a.pre_dbeta0 = dbeta; a.pre_dgamma1 = dgamma_gate; a.pre_dbeta1 = dbeta_gate;
-    rc = mcvc_trunk_launch(a, ks, s);
+    if (ks > 1 && mcvc_deterministic()) {          // no atomics into dx: the K slices one launch after the other (this entry has no slab workspace)
+        a.ky_n = ks;
+        for (a.ky0 = 0; a.ky0 < ks && !rc; ++a.ky0) rc = mcvc_trunk_launch(a, ks, s);
+    } else rc = mcvc_trunk_launch(a, ks, s);
     if (rc || !x_in || !dw) return rc;
     if (KW != 3 || !mcvc_wgrad_smallk_batch_applies(B, T4)) return MCVC_ERR_INVALID;
     SmallKJob jobs[2];

@@ -15,6 +15,8 @@ struct TrunkArgs {
     int accumulate;                         // mode 0 only
     int slab_all;                           // mode 0, K split: EVERY split s writes slabs + s*slab_stride and the destination is left alone
                                             // (deterministic accumulate: the consumer sums destination + all slabs in a fixed order)
+    int ky_n, ky0;                          // mode 0, accumulate, ky_n > 0: the K split as ky_n launches in stream order, each one slice (ky0) with gridDim.y == 1,
+                                            // which adds to the destination with plain loads and stores -- a fixed order without a slab workspace
     float* slabs; long long slab_stride;    // mode 0, K split without accumulate: split s >= 1 writes slabs + (s-1)*slab_stride (the consumer sums)
     float* stats;                           // [B][Mtot][2] (mean, rstd)
     const float* gamma0; const float* beta0; const float* gamma1; const float* beta1;

@@ -96,10 +96,13 @@ __global__ void __launch_bounds__(kTrunkThreads) trunk_layer_kernel(const Twin<T
     const int rows_per_block = glu ? 8 : 16;
     const int r0 = blockIdx.x * rows_per_block;
     // K range of this workgroup (gridDim.y K-splits, accumulate mode only) and of this wave
-    const int kblk = a.K / gridDim.y;
+    // (a.ky_n > 0: the K slices run as ky_n launches of gridDim.y == 1 one after the other, this one being slice a.ky0 -- trunk.h)
+    const int ky_n = a.ky_n > 0 ? a.ky_n : (int)gridDim.y;
+    const int ky = a.ky_n > 0 ? a.ky0 : (int)blockIdx.y;
+    const int kblk = a.K / ky_n;
     const int k_count = kblk / kTrunkWaves;       // multiple of the super-group (checked on the host)
-    const int k_begin = blockIdx.y * kblk + wave * k_count;
-    const int ci_begin = (blockIdx.y * kblk) / KW;
+    const int k_begin = ky * kblk + wave * k_count;
+    const int ci_begin = (ky * kblk) / KW;
     const int ci_count = kblk / KW;
 
     // A row of this lane
@@ -343,7 +346,7 @@ __global__ void __launch_bounds__(kTrunkThreads) trunk_layer_kernel(const Twin<T
             const int b = nn / a.T4, t = nn - b * a.T4;
             float* dst = base + (long long)row_cx(row) * a.c_sc + (long long)b * a.c_sb + t;
             float v = tile[row * TLP + nn];
-            if (a.bias0 && blockIdx.y == 0) v += a.bias0[r0 + row];
+            if (a.bias0 && ky == 0) v += a.bias0[r0 + row];
             if (a.slab_all) *dst = v;
             else if (a.accumulate) { if (gridDim.y > 1) unsafeAtomicAdd(dst, v); else *dst += v; }
             else *dst = v;
@@ -1161,8 +1164,9 @@ int mcvc_trunk_launch(const TrunkArgs& a, int ksplit, hipStream_t s)
     if (ksplit > 1 && !(a.mode == TRUNK_PLAIN && (a.accumulate || a.slabs))) return MCVC_ERR_INVALID;
     if (a.slab_all && !(a.mode == TRUNK_PLAIN && a.slabs)) return MCVC_ERR_INVALID;
     if (a.pre && (a.mode != TRUNK_PLAIN || a.T4 > 32 || !a.pre_x || !a.pre_stats || !a.pre_out || (a.pre_xB > 0 && a.pre_xB < a.B))) return MCVC_ERR_INVALID;
+    if (a.ky_n != 0 && !(a.ky_n == ksplit && a.ky0 >= 0 && a.ky0 < ksplit && a.mode == TRUNK_PLAIN && a.accumulate && !a.slab_all)) return MCVC_ERR_INVALID;
     const int rows = (a.mode == TRUNK_IN_GLU) ? 8 : 16;
-    dim3 grid((unsigned)(a.M / rows), (unsigned)ksplit);
+    dim3 grid((unsigned)(a.M / rows), (unsigned)(a.ky_n > 0 ? 1 : ksplit));
     size_t lds = (size_t)mcvc_trunk_lds_floats(a.Cin, a.KW, a.B, a.T4, ksplit) * sizeof(float);
     if (a.pre) {          // + [channels of a K slice][B][2] row sums behind the staged slice
         const long long xs = (long long)(a.Cin / ksplit) * trunk_rs(a.B, a.T4, a.KW) + 4 + (long long)(a.Cin / ksplit) * a.B * 2;
