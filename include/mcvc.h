@@ -320,6 +320,37 @@ int mcvc_audio_plan(const int* sample_offs, int n_utts, int* frame_offs, int* ti
 int mcvc_audio_log_mel(const float* wave, long long n_samples, const int* tiles, int n_tiles, const float* basis, float* out,
                        long long total_frames, void* stream);
 
+/* ---- MelGAN decoder, log-mel -> waveform (new: the reference ends its inference driver in vocoder.inverse(mel) of the torch.hub MelGAN
+ *      model -- mask_cyclegan_vc/test.py:94-103, utils.py:25-39).  Generator(input_size 80, ngf 32, n_residual_layers 3) of Kumar et al.
+ *      2019 in fp32, inference only: mel [B][80][T] log10-mel -> out [B][256 T], T >= 4 (ReflectionPad1d(3)).  42 weight-normed Conv1d /
+ *      ConvTranspose1d layers in state-dict order: 0 = model.1; stage s = 0..3 starts at 1 + 10 s with its transposed conv, followed per
+ *      residual block by (block.2, block.4, shortcut); 41 = model.24.  One arithmetic, one accumulation order, no atomics: results are
+ *      bit-reproducible whatever mcvc_set_deterministic says, and a sample's result does not depend on its batch.
+ *        mcvc_voc_out_samples       256 T; 0 when T < 4.
+ *        mcvc_voc_launches          kernel launches of one decode (30).
+ *        mcvc_voc_packed_floats     size of the packed weights.
+ *        mcvc_voc_pack              host_table: 42 x (weight, bias) HOST fp32 pointers with weight norm already folded (w = g v / ||v||, the
+ *                                   norm over every dimension but 0), in torch's layouts ([Cout][Cin][k]; transposed: [Cin][Cout][2r]);
+ *                                   packed_host: HOST buffer.  The caller uploads it (16-byte aligned) and keeps it per checkpoint.
+ *        mcvc_voc_workspace_floats  transient activations of one decode; monotone in B and T.
+ *        mcvc_voc_decode            all 30 launches on `stream`; no device allocation.  MCVC_ERR_INVALID: T < 4, B < 1, a misaligned
+ *                                   pointer (packed, workspace, out: 16 bytes); MCVC_ERR_WORKSPACE: workspace too small -- nothing is launched.
+ *      One layer through the same kernels (op-level parity).  kind: 0 Conv1d with reflection padding (k - 1) dilation / 2 (k odd);
+ *      1 ConvTranspose1d(k = 2r, stride r, padding r / 2; r = 2, 4, 8, 16), y [B][Cout][r L]; 2 the stacked residual product
+ *      y = w0 @ x0 + b0 + w1 @ lrelu(x1) + b1 (1 x 1, Cin = Cout); 3 LeakyReLU + Conv1d(Cin, 1, k) + tanh, y [B][L].  act_in: LeakyReLU(0.2)
+ *      on the input of kinds 0 and 1.  Cout * max(r / 2, 1) % 32 == 0 and Cin % 16 == 0, else mcvc_voc_layer_packed_floats returns 0 and
+ *      the others MCVC_ERR_INVALID.  mcvc_voc_layer_pack is HOST -> HOST like mcvc_voc_pack; packed and y are 16-byte aligned DEVICE pointers. */
+int mcvc_voc_out_samples(int T);
+int mcvc_voc_launches(void);
+long long mcvc_voc_packed_floats(void);
+int mcvc_voc_pack(const float* const* host_table, float* packed_host);
+long long mcvc_voc_workspace_floats(int B, int T);
+int mcvc_voc_decode(const float* packed, const float* mel, float* out, float* workspace, long long workspace_floats, int B, int T, void* stream);
+long long mcvc_voc_layer_packed_floats(int kind, int Cin, int Cout, int k, int r);
+int mcvc_voc_layer_pack(int kind, const float* w0, const float* b0, const float* w1, const float* b1, float* packed_host, int Cin, int Cout, int k, int r);
+int mcvc_voc_layer(int kind, const float* packed, const float* x0, const float* x1, float* y, int B, int Cin, int Cout, int L, int k, int dilation, int r,
+                   int act_in, void* stream);
+
 /* ---- single-op entry points (kernel parity tests; same kernels the network calls use) ---------- */
 /* y[N,Cout,OH,OW] = conv2d(x[N,Cin,H,W], w[Cout,Cin,KH,KW]) + bias ; stride 1 or 2.
  * wpack: scratch of mcvc_conv2d_pack_floats() floats, zero-initialised by the caller.

@@ -16,5 +16,8 @@ class CycleGANTestArgParser(BaseArgParser):
         ("--wav_dir", dict(type=str, default=None, help="(new) convert the .wav files of this folder (sorted, recursive) instead of the source speaker's "
                            "preprocessed utterances: mels come from the GPU front-end (data_preprocessing/audio2mel.py) and are standardised with the source "
                            "speaker's norm_stat.npz.  Files not at 22050 Hz are resampled with scipy.signal.resample_poly, which is not librosa's resampler.")),
+        ("--vocoder_ckpt", dict(type=str, default=None, help="(new) state dict of the MelGAN vocoder (torch.hub descriptinc/melgan-neurips, saved with "
+                                "torch.save): converted and original utterances are also decoded to 32-bit float .wav files under converted_audio/.  "
+                                "Without it only converted_mel/*.npy are written.")),
         ("--max_batch", dict(type=int, default=16, help="(new) utterances of identical length are converted in one batched forward of up to this many.")),
     ]

@@ -23,6 +23,7 @@
 #include "sgemm.h"
 #include "sampler.h"
 #include "audio.h"
+#include "vocoder.h"
 #include "../../include/mcvc.h"
 #include <string.h>
 #include <algorithm>
@@ -2697,6 +2698,35 @@ int mcvc_audio_log_mel(const float* wave, long long n_samples, const int* tiles,
                        long long total_frames, void* stream)
 {
     return mcvc_audio_log_mel_launch(wave, n_samples, tiles, n_tiles, basis, out, total_frames, (hipStream_t)stream);
+}
+
+// ---- MelGAN decoder (vocoder_kernels.hip) ----
+int mcvc_voc_out_samples(int T) { return T < MCVC_VOC_MIN_FRAMES || T > (1 << 20) ? 0 : MCVC_VOC_HOP * T; }
+
+int mcvc_voc_launches(void) { return MCVC_VOC_NLAUNCH; }
+
+long long mcvc_voc_packed_floats(void) { return mcvc_voc_packed_floats_of(); }
+
+int mcvc_voc_pack(const float* const* host_table, float* packed_host) { return mcvc_voc_pack_host(host_table, packed_host); }
+
+long long mcvc_voc_workspace_floats(int B, int T) { return mcvc_voc_workspace_floats_of(B, T); }
+
+int mcvc_voc_decode(const float* packed, const float* mel, float* out, float* workspace, long long workspace_floats, int B, int T, void* stream)
+{
+    return mcvc_voc_decode_launch(packed, mel, out, workspace, workspace_floats, B, T, (hipStream_t)stream);
+}
+
+long long mcvc_voc_layer_packed_floats(int kind, int Cin, int Cout, int k, int r) { return mcvc_voc_layer_packed_floats_of(kind, Cin, Cout, k, r); }
+
+int mcvc_voc_layer_pack(int kind, const float* w0, const float* b0, const float* w1, const float* b1, float* packed_host, int Cin, int Cout, int k, int r)
+{
+    return mcvc_voc_layer_pack_host(kind, w0, b0, w1, b1, packed_host, Cin, Cout, k, r);
+}
+
+int mcvc_voc_layer(int kind, const float* packed, const float* x0, const float* x1, float* y, int B, int Cin, int Cout, int L, int k, int dilation, int r,
+                   int act_in, void* stream)
+{
+    return mcvc_voc_layer_launch(kind, packed, x0, x1, y, B, Cin, Cout, L, k, dilation, r, act_in, (hipStream_t)stream);
 }
 
 int mcvc_axpy(float* y, const float* x, float alpha, long long n, void* stream)

@@ -1,8 +1,13 @@
 """``python -m mask_cyclegan_vc.test`` -- drop-in for the reference inference driver (mask_cyclegan_vc/test.py:18-126).
 
 Loads one generator checkpoint and converts every utterance of the source speaker with an all-ones mask
-(test.py:92, 107).  The MelGAN vocoder decode + wav writing of the reference need network access and audio packages
-(out of scope); the converted, de-normalised mel-spectrograms are written as .npy next to where the wavs would go.
+(test.py:92, 107).  The converted, de-normalised mel-spectrograms are always written as .npy under converted_mel/.
+
+``--vocoder_ckpt`` (new): the reference's last step (test.py:94-103).  The MelGAN weights cannot be fetched by this build, so the
+user supplies the hub model's state dict; with it every converted utterance and its de-normalised source are decoded by the HIP MelGAN
+decoder (mask_cyclegan_vc/vocoder.py; one batched ``inverse`` each per bucket, on the bucket's stream) and written under
+converted_audio/ with the reference's file names, as 32-bit float WAV at ``--sample_rate`` (what torchaudio.save writes for a float
+tensor).  The decoder reads exactly the float32 values the .npy files hold.
 
 Batching (new): InstanceNorm statistics run over an utterance's whole time axis, so zero-padding utterances to a common
 length would change every output.  Utterances are therefore bucketed by EXACT length: a bucket of k equal-length utterances
@@ -40,6 +45,12 @@ class MaskCycleGANVCTesting(object):
         self.generator.eval()
         self.saver = ModelSaver(args)
         self.saver.load_model(self.generator, self.model_name)
+        self.vocoder = None
+        if args.vocoder_ckpt:
+            from .vocoder import MelVocoder
+            self.vocoder = MelVocoder.from_checkpoint(args.vocoder_ckpt, self.device)
+            self.converted_audio_dir = os.path.join(args.save_dir, args.name, "converted_audio")
+            os.makedirs(self.converted_audio_dir, exist_ok=True)
 
     def wav_dir_utterances(self, mean, std):
         """--wav_dir: the folder's recordings (sorted) -> log-mels on the GPU (one launch) -> standardised with the SOURCE speaker's
@@ -52,12 +63,23 @@ class MaskCycleGANVCTesting(object):
         mels = Audio2Mel(self.device).bank([read_wav(f) for f in files])
         return [((m - mean) / std).astype(np.float32) for m in mels]
 
+    def write_audio(self, grp, converted, original, tag, st):
+        """The reference's wav pair per utterance (test.py:94-103): both banks of equal-length mels are one batched decode each on the
+        bucket's stream."""
+        from scipy.io import wavfile
+        with torch.cuda.stream(st):
+            wavs = [self.vocoder.inverse(torch.from_numpy(np.stack(m)).to(self.device)).cpu().numpy() for m in (converted, original)]
+        for kind, wav in zip(("converted", "original"), wavs):
+            for j, i in enumerate(grp):
+                wavfile.write(os.path.join(self.converted_audio_dir, "%d-%s_%s.wav" % (i, kind, tag)), int(self.args.sample_rate), wav[j])
+
     def test(self):
         a2b = self.model_name == "generator_A2B"
         src = self.dataset_A if a2b else self.dataset_B
         if self.args.wav_dir:
             src = self.wav_dir_utterances(*((self.dataset_A_mean, self.dataset_A_std) if a2b else (self.dataset_B_mean, self.dataset_B_std)))
         mean, std = (self.dataset_B_mean, self.dataset_B_std) if a2b else (self.dataset_A_mean, self.dataset_A_std)
+        src_mean, src_std = (self.dataset_A_mean, self.dataset_A_std) if a2b else (self.dataset_B_mean, self.dataset_B_std)
         tag = ("%s_to_%s" % (self.args.speaker_A_id, self.args.speaker_B_id)) if a2b else ("%s_to_%s" % (self.args.speaker_B_id, self.args.speaker_A_id))
         outs = [None] * len(src)
         buckets = {}
@@ -72,13 +94,17 @@ class MaskCycleGANVCTesting(object):
             """Write out the oldest groups until at most ``keep`` are in flight: device memory stays bounded by a few groups whatever the
             dataset size (the reference holds one utterance at a time, test.py:85-119)."""
             while len(pending) > keep:
-                grp, fake, _real, ev = pending.pop(0)
+                grp, fake, _real, ev, st = pending.pop(0)
                 ev.synchronize()                              # the group's own stream is done with `fake` and `_real`
                 host = fake.cpu().numpy()
+                mels = [denormalize_mel(host[j], mean, std).astype(np.float32) for j in range(len(grp))]
                 for j, i in enumerate(grp):
                     path = os.path.join(self.converted_dir, "%d-converted_%s.npy" % (i, tag))
-                    np.save(path, denormalize_mel(host[j], mean, std).astype(np.float32))
+                    np.save(path, mels[j])
                     outs[i] = path
+                if self.vocoder is not None:
+                    self.write_audio(grp, mels, [denormalize_mel(np.asarray(src[i], dtype=np.float32), src_mean, src_std).astype(np.float32) for i in grp],
+                                     tag, st)
         with torch.no_grad():
             for T in sorted(buckets, reverse=True):
                 ids = buckets[T]
@@ -91,7 +117,7 @@ class MaskCycleGANVCTesting(object):
                         fake = self.generator.infer(real, None, dtype=self.args.dtype).float()      # all-ones mask (test.py:92)
                         ev = torch.cuda.Event()
                         ev.record(st)
-                    pending.append((grp, fake, real, ev))     # keep `real` alive until the stream is done with it
+                    pending.append((grp, fake, real, ev, st))  # keep `real` alive until the stream is done with it
                     drain(4)                                  # two groups per stream in flight
             drain(0)
             for st in streams:
