@@ -351,6 +351,32 @@ int mcvc_voc_layer_pack(int kind, const float* w0, const float* b0, const float*
 int mcvc_voc_layer(int kind, const float* packed, const float* x0, const float* x1, float* y, int B, int Cin, int Cout, int L, int k, int dilation, int r,
                    int act_in, void* stream);
 
+/* ---- Griffin-Lim decoder, log-mel or linear magnitude -> waveform (new: audio without a vocoder checkpoint).  Phase reconstruction
+ *      against the front-end's own STFT (reflect-pad 384, frames of 1024 at hop 256, periodic Hann w, bins 0..512), fp32, no weights:
+ *        M = max(0, pinv(mel basis) @ 10^logmel), or the linear input;
+ *        ISTFT(S): y[p] = sum_t (w irfft(S[:, t]))[p - 256 t] / sum_t w^2[p - 256 t], kept for p in [384, 384 + 256 T);
+ *        A_0 = angles0 (unit modulus; NULL: zero phase), R_-1 = 0; for k < n_iter: R_k = STFT(ISTFT(M A_k)),
+ *        Z = R_k - momentum / (1 + momentum) R_k-1, A_k+1 = Z / |Z| (0 where Z is 0);  out = ISTFT(M A_n_iter).
+ *      in [B][80][T] (in_kind 0, log10-mel) or [B][513][T] (in_kind 1, magnitude >= 0); angles0 [B][513][T][2] = (re, im); out [B][256 T].
+ *      No atomics, one accumulation order: bit-reproducible, and a sample's result does not depend on its batch.
+ *        mcvc_gl_out_samples       256 T; 0 when T < 2 (256 T >= 385 samples: the front-end's reflect-padding rule).
+ *        mcvc_gl_launches          kernel launches of one decode: 2 n_iter + 3; 0 when n_iter < 0.
+ *        mcvc_gl_tables_floats     size of the constant operand: the inverse DFT basis in the order the kernel's lanes read it, the
+ *                                  pseudo-inverse of the mel basis, the squared window and the front-end's operand (mcvc_audio_basis_init).
+ *        mcvc_gl_tables_init       fills it.  host_pinv: HOST [513][80] fp32, the pseudo-inverse of the [80][513] mel basis, computed by the
+ *                                  caller in float64; host_out: HOST buffer.  The caller uploads it (16-byte aligned) once per device.
+ *        mcvc_gl_workspace_floats  transient state of one decode; monotone in B and T; 0 when B < 1, T < 2, B > 65535 or B T > 2^22.
+ *        mcvc_gl_decode            all launches on `stream`; no device allocation.  MCVC_ERR_INVALID: a null in / tables / out, a misaligned
+ *                                  pointer (in, out: 4 bytes; angles0: 8; tables, workspace: 16), T < 2, B < 1, n_iter < 0, momentum outside
+ *                                  [0, 1), an unknown in_kind; MCVC_ERR_WORKSPACE: workspace null or too small -- nothing is launched.      */
+int mcvc_gl_out_samples(int T);
+int mcvc_gl_launches(int n_iter);
+long long mcvc_gl_tables_floats(void);
+int mcvc_gl_tables_init(const float* host_pinv, float* host_out);
+long long mcvc_gl_workspace_floats(int B, int T);
+int mcvc_gl_decode(const float* in, int in_kind, const float* angles0, const float* tables, float* out, float* workspace,
+                   long long workspace_floats, int B, int T, int n_iter, float momentum, void* stream);
+
 /* ---- single-op entry points (kernel parity tests; same kernels the network calls use) ---------- */
 /* y[N,Cout,OH,OW] = conv2d(x[N,Cin,H,W], w[Cout,Cin,KH,KW]) + bias ; stride 1 or 2.
  * wpack: scratch of mcvc_conv2d_pack_floats() floats, zero-initialised by the caller.

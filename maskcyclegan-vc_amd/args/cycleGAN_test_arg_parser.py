@@ -19,5 +19,16 @@ class CycleGANTestArgParser(BaseArgParser):
         ("--vocoder_ckpt", dict(type=str, default=None, help="(new) state dict of the MelGAN vocoder (torch.hub descriptinc/melgan-neurips, saved with "
                                 "torch.save): converted and original utterances are also decoded to 32-bit float .wav files under converted_audio/.  "
                                 "Without it only converted_mel/*.npy are written.")),
+        ("--griffin_lim", dict(type=int, default=0, metavar="N_ITER", help="(new) decode converted and original utterances to 32-bit float .wav files under "
+                               "converted_audio/ by N_ITER iterations of Griffin-Lim phase reconstruction on the GPU (mask_cyclegan_vc/griffinlim.py): "
+                               "needs no vocoder weights.  0 (default): off.  Not together with --vocoder_ckpt.")),
         ("--max_batch", dict(type=int, default=16, help="(new) utterances of identical length are converted in one batched forward of up to this many.")),
     ]
+
+    def parse_args(self, argv=None):
+        pre = self.parser.parse_args(argv)                             # refused before any run directory is created
+        if pre.griffin_lim < 0:
+            self.parser.error("--griffin_lim takes a number of iterations >= 0")
+        if pre.griffin_lim and pre.vocoder_ckpt:
+            self.parser.error("--griffin_lim and --vocoder_ckpt are two decoders for the same files: give one of them")
+        return super(CycleGANTestArgParser, self).parse_args(argv)

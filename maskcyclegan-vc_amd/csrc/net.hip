@@ -24,6 +24,7 @@
 #include "sampler.h"
 #include "audio.h"
 #include "vocoder.h"
+#include "griffinlim.h"
 #include "../../include/mcvc.h"
 #include <string.h>
 #include <algorithm>
@@ -2727,6 +2728,28 @@ int mcvc_voc_layer(int kind, const float* packed, const float* x0, const float* 
                    int act_in, void* stream)
 {
     return mcvc_voc_layer_launch(kind, packed, x0, x1, y, B, Cin, Cout, L, k, dilation, r, act_in, (hipStream_t)stream);
+}
+
+// ---- Griffin-Lim decoder (griffinlim_kernels.hip) ----
+int mcvc_gl_out_samples(int T) { return mcvc_gl_out_samples_of(T); }
+
+int mcvc_gl_launches(int n_iter) { return mcvc_gl_launches_of(n_iter); }
+
+long long mcvc_gl_tables_floats(void) { return mcvc_gl_tables_floats_of(); }
+
+int mcvc_gl_tables_init(const float* host_pinv, float* host_out)
+{
+    if (!host_pinv || !host_out || ((uintptr_t)host_pinv & 3) || ((uintptr_t)host_out & 3)) return MCVC_ERR_INVALID;
+    mcvc_gl_tables_fill(host_pinv, host_out);
+    return MCVC_OK;
+}
+
+long long mcvc_gl_workspace_floats(int B, int T) { return mcvc_gl_workspace_floats_of(B, T); }
+
+int mcvc_gl_decode(const float* in, int in_kind, const float* angles0, const float* tables, float* out, float* workspace,
+                   long long workspace_floats, int B, int T, int n_iter, float momentum, void* stream)
+{
+    return mcvc_gl_decode_launch(in, in_kind, angles0, tables, out, workspace, workspace_floats, B, T, n_iter, momentum, (hipStream_t)stream);
 }
 
 int mcvc_axpy(float* y, const float* x, float alpha, long long n, void* stream)

@@ -108,6 +108,12 @@ _SIGS = {
     "mcvc_voc_layer_packed_floats": (c_longlong, [c_int] * 5),
     "mcvc_voc_layer_pack": (c_int, [c_int] + [c_void_p] * 5 + [c_int] * 4),
     "mcvc_voc_layer": (c_int, [c_int] + [c_void_p] * 4 + [c_int] * 8 + [c_void_p]),
+    "mcvc_gl_out_samples": (c_int, [c_int]),
+    "mcvc_gl_launches": (c_int, [c_int]),
+    "mcvc_gl_tables_floats": (c_longlong, []),
+    "mcvc_gl_tables_init": (c_int, [c_void_p, c_void_p]),
+    "mcvc_gl_workspace_floats": (c_longlong, [c_int, c_int]),
+    "mcvc_gl_decode": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_float, c_void_p]),
     "mcvc_axpy": (c_int, [c_void_p, c_void_p, c_float, c_longlong, c_void_p]),
     "mcvc_conv2d_pack_floats": (c_longlong, [c_int, c_int, c_int, c_int]),
     "mcvc_conv2d_forward": (c_int, [c_void_p] * 6 + [c_int] * 12 + [c_void_p]),

@@ -15,6 +15,10 @@ is one batched forward (up to ``--max_batch``; every op is per-sample, so result
 visited longest first and alternate between two HIP streams so that short utterances overlap on the chip.  ``--dtype bf16``
 selects the bf16-MFMA forward (BASELINE configs[4]).
 
+``--griffin_lim N_ITER`` (new): the same two files per utterance without any vocoder weights -- N_ITER iterations of Griffin-Lim phase
+reconstruction against the front-end's own STFT (mask_cyclegan_vc/griffinlim.py, csrc/griffinlim_kernels.hip), through the same
+``write_audio`` path.  Not together with ``--vocoder_ckpt``; with neither flag no audio is written and neither decoder is imported.
+
 ``--wav_dir`` (new): the utterances to convert are the .wav files of a folder instead of the source speaker's pickle; their
 mel-spectrograms come from the GPU front-end (data_preprocessing/audio2mel.py)."""
 import os
@@ -49,6 +53,10 @@ class MaskCycleGANVCTesting(object):
         if args.vocoder_ckpt:
             from .vocoder import MelVocoder
             self.vocoder = MelVocoder.from_checkpoint(args.vocoder_ckpt, self.device)
+        elif getattr(args, "griffin_lim", 0) > 0:
+            from .griffinlim import GriffinLimVocoder
+            self.vocoder = GriffinLimVocoder(self.device, n_iter=args.griffin_lim)
+        if self.vocoder is not None:
             self.converted_audio_dir = os.path.join(args.save_dir, args.name, "converted_audio")
             os.makedirs(self.converted_audio_dir, exist_ok=True)
 

@@ -13,7 +13,8 @@ def _out_of_scope(name):
 
 
 def decode_melspectrogram(vocoder, melspectrogram, mel_mean, mel_std):
-    """[80, T] standardised mel -> [1, 256 T] waveform (reference utils.py:37-39)."""
+    """[80, T] standardised mel -> [1, 256 T] waveform (reference utils.py:37-39).  ``vocoder`` is any object with an ``inverse``
+    that takes a [B, 80, T] log10-mel: ``vocoder.MelVocoder`` (trained weights) or ``griffinlim.GriffinLimVocoder`` (none needed)."""
     denorm_converted = melspectrogram * mel_std + mel_mean
     rev = vocoder.inverse(denorm_converted.unsqueeze(0))
     return rev
