@@ -68,7 +68,7 @@ struct Exec {
     int br1_on_main = 0;           // conv_wgrad: run the gate branch's generic weight gradient on the main stream (see there)
     int no_join = 0;               // backward pass: leave the auxiliary stream un-joined at the end (mcvc_gen_backward_flags)
     int fuse_next = 0;             // the caller's next step is a norm that can absorb a Winograd output transform (set before conv_fwd)
-    int pend_pts = 0;              // 16 / 36 / 43 (= F(4x4,3x3)) / 64: the output transform in `pend` has not run yet -- norm_fwd runs it (fused when it fits)
+    const struct WinoFam* pend_fam = nullptr;   // the output transform of this family in `pend` has not run yet -- norm_fwd runs it (fused when it fits)
     WinoOutArgs pend;
     int y_xs_pw = 0; long long y_xs_plane = 0;   // the next norm_fwd writes y in the phase-split padded layout (sgemm.h); consumed by norm_fwd
     int dx_pitch = 0;              // the next norm_bwd writes dx in the padded dY layout (rows of dx_pitch floats + a zero row); consumed by norm_bwd
@@ -359,7 +359,7 @@ static bool wino43_applies(const Exec& ex, const ConvSpec& c, int NB, int OH, in
     return c.wino3 && c.off_w43 >= 0 && wino43_min_nb() > 0 && NB >= wino43_min_nb() && (OH & 3) == 0 && (OW & 3) == 0 && !(ex.pack_skips & 32);
 }
 // samples per F(4x4) pass: V / M hold pts * max(K, M) * tiles floats
-static int wino4_chunk(const Exec& ex, int NB, long long tiles_per_sample, int KM, int pts = 64)
+static int wino4_chunk(const Exec& ex, int NB, long long tiles_per_sample, int KM, int pts)
 {
     const long long cap_tiles = (ex.wino_cap / ((long long)pts * KM)) & ~31LL;
     if (tiles_per_sample <= 0 || cap_tiles < tiles_per_sample) return 0;
@@ -369,89 +369,205 @@ static int wino4_chunk(const Exec& ex, int NB, long long tiles_per_sample, int K
     return (int)((NB + nch - 1) / nch);
 }
 
-static bool conv_wino4(Exec& ex, const ConvSpec& c, const float* packed, int dgrad, int NB, int H, int W, CView x, View y, int shuffle, int accumulate)
+// ---- the four Winograd families ------------------------------------------------------------------------------------------------------------
+// What the passes below differ in from family to family.  The phase-form launchers (a stride-2 5x5 layer as a 3x3 convolution over the four
+// input phases) take the original image's size on top; the 5x5 families serve one-branch layers, so their dw launcher has no gate tensor.
+struct WinoFam {
+    int pts;             // transform points: batched products per pass, matrices per weight set
+    int nxi;             // ... as WinoGemmArgs::nxi names them (0 = the launcher's default, 36)
+    int tile;            // side of an output tile
+    int pad;             // padding of the stride-1 convolution
+    int min_pitch;       // smallest tile pitch of V / M in a forward / data-gradient pass
+    int norm_pts;        // the family's name in mcvc_norm_fwd_wino_applies / _launch (wino.h)
+    int (*input)(const WinoXformArgs&, hipStream_t);
+    int (*input_phase)(const WinoXformArgs&, int XH, int XW, hipStream_t);
+    int (*output)(const WinoOutArgs&, hipStream_t);
+    int (*input_t)(const WinoXformArgs&, hipStream_t);                          // the weight gradient's tile-major operands ...
+    int (*input_phase_t)(const WinoXformArgs&, int XH, int XW, hipStream_t);
+    int (*dy_t)(const WinoXformArgs&, hipStream_t);
+    int (*dw)(const float* du, float* dw0, float* dw1, int Cout, int nbr, int Cin, hipStream_t);      // ... and dW += G^T dU G
+};
+enum { kF23, kF25, kF43, kF45 };          // F(2x2,3x3), F(2x2,5x5), F(4x4,3x3), F(4x4,5x5)
+static const WinoFam kWino[4] = {
+    {16, 16, 2, 1, 32, 16, mcvc_wino3_input_launch, mcvc_wino3_input_phase_launch, mcvc_wino3_output_launch,
+     nullptr, mcvc_wino3_input_phase_t_launch, mcvc_wino3_dy_t_launch, mcvc_wino3_dw_launch},
+    {36, 0, 2, 2, 32, 36, mcvc_wino_input_launch, nullptr, mcvc_wino_output_launch,
+     mcvc_wino_input_t_launch, nullptr, mcvc_wino_dy_t_launch,
+     [](const float* du, float* dw0, float*, int Cout, int, int Cin, hipStream_t s) { return mcvc_wino_dw_launch(du, dw0, Cout, Cin, s); }},
+    {36, 36, 4, 1, 32, 43, mcvc_wino43_input_launch, mcvc_wino43_input_phase_launch, mcvc_wino43_output_launch,
+     nullptr, mcvc_wino43_input_phase_t_launch, mcvc_wino43_dy_t_launch, mcvc_wino43_dw_launch},
+    {64, 64, 4, 2, 64 /* (the GEMM wants a pitch of 64+ columns) */, 64, mcvc_wino4_input_launch, nullptr, mcvc_wino4_output_launch,
+     mcvc_wino4_input_t_launch, nullptr, mcvc_wino4_dy_t_launch,
+     [](const float* du, float* dw0, float*, int Cout, int, int Cin, hipStream_t s) { return mcvc_wino4_dw_launch(du, dw0, Cout, Cin, s); }},
+};
+static long long wino_tiles(const WinoFam& f, int H, int W) { return (long long)((H + f.tile - 1) / f.tile) * ((W + f.tile - 1) / f.tile); }
+
+// Samples per pass of family f over NB samples of `tiles` tiles each and max(K, M) = KM channels; 0 = the family does not apply.
+// 4x4 tiles: capacity by wino4_chunk, at least min_tiles real tiles per pass unless the op-level entry forces the scheme.
+// 2x2 tiles: the largest chunk's padded tile count fits wino_cap and reaches min_tiles (no exemption).
+static int wino_nbc(const Exec& ex, const WinoFam& f, int NB, long long tiles, int KM, int min_tiles)
 {
-    const int K = dgrad ? c.cout_tot : c.Cin, M = dgrad ? c.Cin : c.cout_tot;
-    const int TH = H / 4, TW = W / 4;
-    if ((M % 128) != 0 || (K % 16) != 0) return false;
-    const int nbc = wino4_chunk(ex, NB, (long long)TH * TW, K > M ? K : M);
-    if (!nbc || ((long long)nbc * TH * TW < wino4_min_tiles() && ex.force_scheme != 2)) return false;
-    if (ex.dry) return true;
-    for (int b0 = 0; b0 < NB; b0 += nbc) {
-        const int nb = NB - b0 < nbc ? NB - b0 : nbc;
-        const long long NT = (long long)nb * TH * TW, NTp = NT <= 64 ? 64 : ((NT + 31) & ~31LL);      // (the GEMM wants a pitch of 64+ columns)
-        WinoXformArgs xi{};
-        xi.x = x.p + (long long)b0 * x.sb; xi.x_sb = x.sb; xi.x_sc = x.sc; xi.x_sh = x.sh; xi.v = ex.wv;
-        xi.N = nb; xi.C = K; xi.H = H; xi.W = W; xi.TH = TH; xi.TW = TW; xi.NT = (int)NT; xi.NTp = (int)NTp; xi.pad = 2;
-        ex.fail(mcvc_wino4_input_launch(xi, ex.s));
-        WinoGemmArgs ga{};
-        ga.a = packed + (dgrad ? c.off_w4d : c.off_w4f); ga.a_xi = dgrad ? c.wd_xi : c.wf_xi; ga.lda = dgrad ? c.cin_pk : c.cout_pk;
-        ga.b = ex.wv; ga.b_xi = (long long)K * NTp; ga.ldb = (int)NTp;
-        ga.c = ex.wm; ga.c_xi = (long long)M * NTp; ga.ldc = (int)NTp;
-        ga.M = M; ga.N = (int)NTp; ga.K = K; ga.nxi = 64;
-        ex.fail(mcvc_wino_gemm_launch(ga, ex.s));
-        WinoOutArgs oa{};
-        oa.m = ex.wm; oa.bias = dgrad ? nullptr : packed + c.off_bias;
-        oa.y = y.p + (long long)b0 * y.sb; oa.y_sb = y.sb; oa.y_sc = y.sc; oa.y_sh = y.sh;
-        oa.N = nb; oa.Cout = M; oa.OH = H; oa.OW = W; oa.TH = TH; oa.TW = TW; oa.NT = (int)NT; oa.NTp = (int)NTp;
-        oa.shuffle = shuffle; oa.YH = 2 * H; oa.YW = 2 * W; oa.accumulate = accumulate;
-        if (ex.fuse_next && !dgrad && shuffle && nbc == NB) { ex.pend = oa; ex.pend_pts = 64; }
-        else ex.fail(mcvc_wino4_output_launch(oa, ex.s));
+    if (f.tile == 4) {
+        const int nbc = wino4_chunk(ex, NB, tiles, KM, f.pts);
+        return (nbc && (nbc * tiles >= min_tiles || ex.force_scheme == 2)) ? nbc : 0;
     }
-    return true;
+    const int nbc = wino_chunk(NB, tiles);
+    const long long NTc = wino_chunk_tiles(NB, tiles);
+    return (nbc && NTc >= min_tiles && f.pts * NTc * KM <= ex.wino_cap) ? nbc : 0;
 }
 
-static bool conv_wino(Exec& ex, const ConvSpec& c, const float* packed, int dgrad, int NB, int H, int W, CView x, View y, int shuffle,
-                      int accumulate)
+// One forward / data-gradient pass, in chunks of nbc samples: input transform -> f.pts batched [M x K] x [K x tiles] products -> output transform.
+struct WinoPass {
+    const WinoFam* f;
+    int K, M;                                           // input / output channels of the stride-1 convolution
+    int NB, nbc;
+    int H, W;                                           // its image = output size (phase form: the phase planes')
+    int XH, XW;                                         // phase form: the original image x addresses; 0 = x is the image itself
+    const float* a; long long a_xi; int lda, a_rows;    // weight set U[pts][a_rows (+ pad row)][lda]
+    const float* bias;
+    int shuffle, YH, YW, accumulate;                    // the store (WinoOutArgs)
+    bool may_defer;                                     // the output transform may be left to the next norm_fwd
+};
+static void wino_pass(Exec& ex, const WinoPass& p, CView x, View y)
 {
-    if (!c.wino || !wino_enabled() || !ex.wv) return false;
-    if (wino4_applies(ex, c, NB, H, W) && conv_wino4(ex, c, packed, dgrad, NB, H, W, x, y, shuffle, accumulate)) return true;
-    // (bits 128 / 256: the 36-point sets of upSample1 / upSample2 were not refreshed -- gen_pack_cfg skips them for a layer whose EVERY pass at
-    //  the engine's frame count takes the 4 x 4 scheme; recorded per LAYER, so a pass at another frame count on the same packed buffer that
-    //  does reach this path reads no stale set: ADVICE r5)
-    if (!ex.dry && (ex.pack_skips & (c.Cout == 1024 ? 128 : 256))) { ex.fail(MCVC_ERR_INVALID); return true; }
-    const int K = dgrad ? c.cout_tot : c.Cin, M = dgrad ? c.Cin : c.cout_tot;
-    const int TH = (H + 1) / 2, TW = (W + 1) / 2;
-    const int nbc = wino_chunk(NB, (long long)TH * TW);
-    if (!nbc || 36LL * (K > M ? K : M) * wino_chunk_tiles(NB, (long long)TH * TW) > ex.wino_cap) return false;
-    if (ex.dry) return true;
-    static const int own_gemm = mcvc_knob("MCVC_WINO_GEMM", 1);
-    for (int b0 = 0; b0 < NB; b0 += nbc) {
-        const int nb = NB - b0 < nbc ? NB - b0 : nbc;
-        const long long NT = (long long)nb * TH * TW;
-        // the 36 products see the tiles as a (NTp/32) x 32 "image" so that the conv kernel's 2-D pixel tiles are full
-        const long long NTp = (NT + 31) & ~31LL;
+    const WinoFam& f = *p.f;
+    const int K = p.K, M = p.M, TH = (p.H + f.tile - 1) / f.tile, TW = (p.W + f.tile - 1) / f.tile;
+    for (int b0 = 0; b0 < p.NB; b0 += p.nbc) {
+        const int nb = p.NB - b0 < p.nbc ? p.NB - b0 : p.nbc;
+        const long long NT = (long long)nb * TH * TW, NTp = std::max<long long>((NT + 31) & ~31LL, f.min_pitch);
         WinoXformArgs xi{};
         xi.x = x.p + (long long)b0 * x.sb; xi.x_sb = x.sb; xi.x_sc = x.sc; xi.x_sh = x.sh; xi.v = ex.wv;
-        xi.N = nb; xi.C = K; xi.H = H; xi.W = W; xi.TH = TH; xi.TW = TW; xi.NT = (int)NT; xi.NTp = (int)NTp; xi.pad = 2;
-        ex.fail(mcvc_wino_input_launch(xi, ex.s));
-        if (own_gemm && (M % 128) == 0 && (K % 16) == 0 && NTp >= 64) {
+        xi.N = nb; xi.C = K; xi.H = p.H; xi.W = p.W; xi.TH = TH; xi.TW = TW; xi.NT = (int)NT; xi.NTp = (int)NTp; xi.pad = f.pad;
+        ex.fail(p.XH ? f.input_phase(xi, p.XH, p.XW, ex.s) : f.input(xi, ex.s));
+        static const int own_gemm = mcvc_knob("MCVC_WINO_GEMM", 1);
+        if (&f != &kWino[kF25] || (own_gemm && (M % 128) == 0 && (K % 16) == 0 && NTp >= 64)) {
             WinoGemmArgs ga{};
-            ga.a = packed + (dgrad ? c.off_wd : c.off_wf); ga.a_xi = dgrad ? c.wd_xi : c.wf_xi; ga.lda = dgrad ? c.cin_pk : c.cout_pk;
+            ga.a = p.a; ga.a_xi = p.a_xi; ga.lda = p.lda;
             ga.b = ex.wv; ga.b_xi = (long long)K * NTp; ga.ldb = (int)NTp;
             ga.c = ex.wm; ga.c_xi = (long long)M * NTp; ga.ldc = (int)NTp;
-            ga.M = M; ga.N = (int)NTp; ga.K = K;
+            ga.M = M; ga.N = (int)NTp; ga.K = K; ga.nxi = f.nxi;
             ex.fail(mcvc_wino_gemm_launch(ga, ex.s));
         } else {
-            ConvProblem p{K, (int)(NTp / 32), 32, M, (int)(NTp / 32), 32, 1, 1, 1, 0, 0};
+            // F(2x2,5x5) outside the GEMM's shapes: one launch of the direct-conv kernel as a 1x1 conv over 36 images with per-image weights;
+            // the 36 products see the tiles as a (NTp/32) x 32 "image" so that the conv kernel's 2-D pixel tiles are full
+            ConvProblem cp{K, (int)(NTp / 32), 32, M, (int)(NTp / 32), 32, 1, 1, 1, 0, 0};
             ConvIO io{};
             io.x = ex.wv; io.x_sb = (long long)K * NTp; io.x_sc = NTp; io.x_sh = 32;
             io.y = ex.wm; io.y_sb = (long long)M * NTp; io.y_sc = NTp; io.y_sh = 32; io.y_sw = 1;
             io.nsplit = 1;
-            io.w_nstride = dgrad ? c.wd_xi : c.wf_xi;
+            io.w_nstride = p.a_xi;
             io.tile_cfg = wino_tile_cfg(M, NT);
             io.gemm_ok = 1;
-            ex.fail(mcvc_conv_launch(p, 36, io, packed + (dgrad ? c.off_wd : c.off_wf), dgrad ? c.dg_rows_co : c.cin_pad, dgrad ? c.cin_pk : c.cout_pk,
-                                     nullptr, ex.s, nullptr));
+            ex.fail(mcvc_conv_launch(cp, 36, io, p.a, p.a_rows, p.lda, nullptr, ex.s, nullptr));
         }
         WinoOutArgs oa{};
-        oa.m = ex.wm; oa.bias = dgrad ? nullptr : packed + c.off_bias;
+        oa.m = ex.wm; oa.bias = p.bias;
         oa.y = y.p + (long long)b0 * y.sb; oa.y_sb = y.sb; oa.y_sc = y.sc; oa.y_sh = y.sh;
-        oa.N = nb; oa.Cout = M; oa.OH = H; oa.OW = W; oa.TH = TH; oa.TW = TW; oa.NT = (int)NT; oa.NTp = (int)NTp;
-        oa.shuffle = shuffle; oa.YH = 2 * H; oa.YW = 2 * W; oa.accumulate = accumulate;
-        if (ex.fuse_next && !dgrad && shuffle && nbc == NB) { ex.pend = oa; ex.pend_pts = 36; }
-        else ex.fail(mcvc_wino_output_launch(oa, ex.s));
+        oa.N = nb; oa.Cout = M; oa.OH = p.H; oa.OW = p.W; oa.TH = TH; oa.TW = TW; oa.NT = (int)NT; oa.NTp = (int)NTp;
+        oa.shuffle = p.shuffle; oa.YH = p.YH; oa.YW = p.YW; oa.accumulate = p.accumulate;
+        if (p.may_defer && ex.fuse_next && p.nbc == p.NB) { ex.pend = oa; ex.pend_fam = &f; }
+        else ex.fail(f.output(oa, ex.s));
     }
+}
+
+// One weight-gradient pass on stream ws, in chunks of nbc samples: the tile-major operands Vt[xi][tile][ci] from x and dMt[xi][tile][co] = A dY A^T,
+// f.pts products dU[xi] = dMt[xi]^T Vt[xi] over the tiles, then dW += G^T dU G -- the chunks add up in dw.  A stride-2 layer runs in the phase
+// formulation (see conv_wino3): dU[xi][co][4ci+2p+q], both branches (value | gate) in one product, the 3x3 blocks scattered back into the two
+// 5x5 gradients.
+static void wino_wgrad_pass(Exec& ex, const WinoFam& f, const ConvSpec& c, float* const* grads, int NB, int nbc, int H, int W, CView x, CView dy,
+                            hipStream_t ws)
+{
+    const bool phase = c.stride == 2;
+    const int IH = phase ? H / 2 : H, IW = phase ? W / 2 : W, N = phase ? 4 * c.Cin : c.Cin, M = c.cout_tot;
+    const int TH = (IH + f.tile - 1) / f.tile, TW = (IW + f.tile - 1) / f.tile;
+    for (int b0 = 0; b0 < NB; b0 += nbc) {
+        const int nb = NB - b0 < nbc ? NB - b0 : nbc;
+        const long long NT = (long long)nb * TH * TW, NTp = (NT + 31) & ~31LL;
+        WinoXformArgs xi{};
+        xi.x = x.p + (long long)b0 * x.sb; xi.x_sb = x.sb; xi.x_sc = x.sc; xi.x_sh = x.sh; xi.v = ex.wv2;
+        xi.N = nb; xi.C = N; xi.H = IH; xi.W = IW; xi.TH = TH; xi.TW = TW; xi.NT = (int)NT; xi.NTp = (int)NTp; xi.pad = f.pad;
+        ex.fail(phase ? f.input_phase_t(xi, H, W, ws) : f.input_t(xi, ws));
+        WinoXformArgs di{};
+        di.x = dy.p + (long long)b0 * dy.sb; di.x_sb = dy.sb; di.x_sc = dy.sc; di.x_sh = dy.sh; di.v = ex.wm2;
+        di.N = nb; di.C = M; di.H = IH; di.W = IW; di.TH = TH; di.TW = TW; di.NT = (int)NT; di.NTp = (int)NTp; di.pad = 0;
+        ex.fail(f.dy_t(di, ws));
+        WinoGemmArgs ga{};
+        ga.a = ex.wm2; ga.a_xi = NTp * M; ga.lda = M;
+        ga.b = ex.wv2; ga.b_xi = NTp * N; ga.ldb = N;
+        ga.c = ex.wu; ga.c_xi = (long long)M * N; ga.ldc = N;
+        // (rows [NT, NTp) of the tile-major operands are zeros: contract over the 16-row stages that hold tiles -- 80 instead of 96 at one sample)
+        ga.M = M; ga.N = N; ga.K = (int)((NT + 15) & ~15LL); ga.nxi = f.nxi;
+        ex.fail(mcvc_wino_gemm_launch(ga, ws));
+        ex.fail(f.dw(ex.wu, grads[c.wi[0]], c.nbr == 2 ? grads[c.wi[1]] : nullptr, c.Cout, c.nbr, c.Cin, ws));
+    }
+}
+
+// 5x5 stride-1 conv (upSample1/2; see above wino4_min_nb): F(4x4,5x5) where it applies, else F(2x2,5x5)
+static bool conv_wino(Exec& ex, const ConvSpec& c, const float* packed, int dgrad, int NB, int H, int W, CView x, View y, int shuffle,
+                      int accumulate)
+{
+    if (!c.wino || !wino_enabled() || !ex.wv) return false;
+    const int K = dgrad ? c.cout_tot : c.Cin, M = dgrad ? c.Cin : c.cout_tot;
+    const WinoFam* f = &kWino[kF45];
+    int nbc = 0;
+    if (wino4_applies(ex, c, NB, H, W) && (M % 128) == 0 && (K % 16) == 0) nbc = wino_nbc(ex, *f, NB, wino_tiles(*f, H, W), K > M ? K : M, wino4_min_tiles());
+    if (!nbc) {
+        // (bits 128 / 256: the 36-point sets of upSample1 / upSample2 were not refreshed -- gen_pack_cfg skips them for a layer whose EVERY pass at
+        //  the engine's frame count takes the 4 x 4 scheme; recorded per LAYER, so a pass at another frame count on the same packed buffer that
+        //  does reach this path reads no stale set: ADVICE r5)
+        if (!ex.dry && (ex.pack_skips & (c.Cout == 1024 ? 128 : 256))) { ex.fail(MCVC_ERR_INVALID); return true; }
+        f = &kWino[kF25];
+        nbc = wino_nbc(ex, *f, NB, wino_tiles(*f, H, W), K > M ? K : M, 0);
+    }
+    if (!nbc) return false;
+    if (ex.dry) return true;
+    const bool four = f->tile == 4;
+    WinoPass p{};
+    p.f = f; p.K = K; p.M = M; p.NB = NB; p.nbc = nbc; p.H = H; p.W = W;
+    p.a = packed + (dgrad ? (four ? c.off_w4d : c.off_wd) : (four ? c.off_w4f : c.off_wf));
+    p.a_xi = dgrad ? c.wd_xi : c.wf_xi; p.lda = dgrad ? c.cin_pk : c.cout_pk; p.a_rows = dgrad ? c.dg_rows_co : c.cin_pad;
+    p.bias = dgrad ? nullptr : packed + c.off_bias;
+    p.shuffle = shuffle; p.YH = 2 * H; p.YW = 2 * W; p.accumulate = accumulate;
+    p.may_defer = !dgrad && shuffle;
+    wino_pass(ex, p, x, y);
+    return true;
+}
+
+// 5x5 stride-2 padding-2 conv (downSample1/2) as a 3x3 stride-1 conv: F(4x4,3x3) (36 points per 16 outputs) where it applies, else F(2x2,3x3).
+// Forward (H, W even): over the four input phases, K = 4*Cin.  dgrad: the merged data gradient = a conv over dY with 4*Cin output channels and a
+// PixelShuffle store into dX; x is dY and y is dX there.  (c.wino3 says 4*Cin % 128 == 0 and cout_tot % 16 == 0: the GEMM's shapes hold for
+// the data gradient; these layers' OH x OW is ceil(H/2) x ceil(W/2), what the merged form stores.)
+static bool conv_wino3(Exec& ex, const ConvSpec& c, const float* packed, int dgrad, int NB, int H, int W, CView x, View y, int accumulate)
+{
+    if (!c.wino3 || !wino_enabled() || !ex.wv) return false;
+    if (!dgrad && ((H & 1) != 0 || (W & 1) != 0 || (c.cout_tot % 128) != 0)) return false;
+    static const int en[2] = {mcvc_knob("MCVC_WINO3_FWD", 1), mcvc_knob("MCVC_WINO3", 1)};
+    if (!en[dgrad]) return false;
+    const int OH = conv_out(H, c.KH, c.stride, c.ph), OW = conv_out(W, c.KW, c.stride, c.pw);
+    const int K = dgrad ? c.cout_tot : 4 * c.Cin, M = dgrad ? 4 * c.Cin : c.cout_tot;
+    const WinoFam* f = &kWino[kF43];
+    int nbc = 0;
+    if (wino43_applies(ex, c, NB, OH, OW) && 2 * OH == H && 2 * OW == W) nbc = wino_nbc(ex, *f, NB, wino_tiles(*f, OH, OW), K > M ? K : M, 64);
+    if (!nbc) {
+        f = &kWino[kF23];
+        nbc = wino_nbc(ex, *f, NB, wino_tiles(*f, OH, OW), K > M ? K : M, 64);
+    }
+    if (!nbc) return false;
+    if (ex.dry) return true;
+    const bool four = f->tile == 4;
+    WinoPass p{};
+    p.f = f; p.K = K; p.M = M; p.NB = NB; p.nbc = nbc; p.H = OH; p.W = OW;
+    if (dgrad) {
+        p.a = packed + (four ? c.off_w43 : c.off_w3); p.a_xi = c.w3_xi; p.lda = c.mg_ld;
+        p.shuffle = 1; p.YH = H; p.YW = W; p.accumulate = accumulate;
+    } else {
+        p.XH = H; p.XW = W;
+        p.a = packed + (four ? c.off_w43f : c.off_w3f); p.a_xi = c.w3f_xi; p.lda = c.cout_pk;
+        p.bias = packed + c.off_bias;
+        p.YH = OH; p.YW = OW;
+        p.may_defer = true;
+    }
+    wino_pass(ex, p, x, y);
     return true;
 }
 
@@ -503,6 +619,17 @@ static bool igemm_applies(const ConvSpec& c, int H, int W)
 {
     return igemm_enabled() && c.igemm && (H & 1) == 0 && (W & 1) == 0 && ((W / 2) & 3) == 0 && H >= 2 && W >= 8;
 }
+// where the nine taps of such a layer start in its input's phase-split padded layout: tap (kh, kw) of output (oh, ow) reads x[2 oh + kh - 1][2 ow + kw - 1]
+static void xs_tap_offsets(int H, int W, long long boff[9])
+{
+    const int pw = mcvc_xs_pw(W);
+    const long long plane = mcvc_xs_plane(H, W);
+    for (int kh = 0; kh < 3; ++kh)
+        for (int kw = 0; kw < 3; ++kw) {
+            const int ph = (kh == 1) ? 0 : 1, di = (kh == 0) ? -1 : 0, pq = (kw == 1) ? 0 : 1, dj = (kw == 0) ? -1 : 0;
+            boff[3 * kh + kw] = (long long)(2 * ph + pq) * plane + (long long)(1 + di) * pw + 4 + dj;
+        }
+}
 // K split: enough 64 x 64 tiles x classes x splits to occupy the chip, at least two 32-deep stages per split of the shortest class
 static int igemm_split(long long tiles, int Kmin) { return split_by_cost(tiles, Kmin); }
 // forward: xs = the input in the phase-split padded layout, y = the conv output (dense planes); K-split slabs 1.. are summed by the consumer
@@ -522,12 +649,8 @@ static void conv_fwd_igemm(Exec& ex, const ConvSpec& c, const float* packed, int
     IGemmArgs g{};
     g.ncls = 1;
     g.cls[0].a = packed + c.off_ifwd; g.cls[0].ntaps = 9; g.cls[0].coff = 0;
-    for (int kh = 0; kh < 3; ++kh)
-        for (int kw = 0; kw < 3; ++kw) {          // tap (kh, kw) of output (oh, ow) reads x[2 oh + kh - 1][2 ow + kw - 1]
-            const int ph = (kh == 1) ? 0 : 1, di = (kh == 0) ? -1 : 0, pq = (kw == 1) ? 0 : 1, dj = (kw == 0) ? -1 : 0;
-            g.cls[0].boff[3 * kh + kw] = (long long)(2 * ph + pq) * plane + (long long)(1 + di) * pw + 4 + dj;
-            g.cls[0].aoff[3 * kh + kw] = (long long)(3 * kh + kw) * c.Cin * c.cout_pk;      // tap-major copy: rows (tap, ci)
-        }
+    xs_tap_offsets(H, W, g.cls[0].boff);
+    for (int t = 0; t < 9; ++t) g.cls[0].aoff[t] = (long long)t * c.Cin * c.cout_pk;      // tap-major copy: rows (tap, ci)
     g.a_ks = c.cout_pk;
     g.b = xs; g.b_cs = 4 * plane; g.b_sn = (long long)c.Cin * 4 * plane; g.b_pitch = pw; g.Cb = c.Cin; g.OW = OW; g.P = P;
     g.c = y.p; g.ldc = y.sc; g.c_sn = y.sb; g.c_sh = y.sh; g.c_sw = 1;
@@ -574,6 +697,14 @@ static void conv_dgrad_igemm(Exec& ex, const ConvSpec& c, const float* packed, i
     ex.fail(mcvc_igemm_launch(g, ex.s));
 }
 
+// the direct kernels are next, and the last re-pack skipped the copies they read (pack_skips bit 0 / bit 1): fail the pass instead
+static bool stale_direct(Exec& ex, const ConvSpec& c)
+{
+    if (ex.dry || !(((ex.pack_skips & 1) && c.off_tk >= 0) || ((ex.pack_skips & 2) && (c.wino || c.wino3)))) return false;
+    ex.fail(MCVC_ERR_INVALID);
+    return true;
+}
+
 static void conv_fwd(Exec& ex, const ConvSpec& c, const float* packed, int NB, int H, int W, CView x, View y, long long y_total,
                      int shuffle, int allow_split, int* nsplit)
 {
@@ -616,75 +747,8 @@ static void conv_fwd(Exec& ex, const ConvSpec& c, const float* packed, int NB, i
             return;
         }
     }
-    if (conv_wino(ex, c, packed, 0, NB, H, W, x, y, shuffle, 0)) { if (nsplit) *nsplit = 1; return; }
-    if (c.wino3 && wino_enabled() && ex.wv && !shuffle && (H & 1) == 0 && (W & 1) == 0 && (c.cout_tot % 128) == 0 && wino43_applies(ex, c, NB, H / 2, W / 2)) {
-        // ... as F(4x4,3x3): 36 points per 16 outputs
-        static const int en = mcvc_knob("MCVC_WINO3_FWD", 1);
-        const int OH = H / 2, OW = W / 2, K = 4 * c.Cin, M = c.cout_tot;
-        const int TH = OH / 4, TW = OW / 4;
-        const int nbc = wino4_chunk(ex, NB, (long long)TH * TW, K > M ? K : M, 36);
-        if (en && nbc && ((long long)nbc * TH * TW >= 64 || ex.force_scheme == 2)) {
-            if (nsplit) *nsplit = 1;
-            if (ex.dry) return;
-            for (int b0 = 0; b0 < NB; b0 += nbc) {
-                const int nb = NB - b0 < nbc ? NB - b0 : nbc;
-                const long long NT = (long long)nb * TH * TW, NTp = (NT + 31) & ~31LL;
-                WinoXformArgs xi{};
-                xi.x = x.p + (long long)b0 * x.sb; xi.x_sb = x.sb; xi.x_sc = x.sc; xi.x_sh = x.sh; xi.v = ex.wv;
-                xi.N = nb; xi.C = K; xi.H = OH; xi.W = OW; xi.TH = TH; xi.TW = TW; xi.NT = (int)NT; xi.NTp = (int)NTp; xi.pad = 1;
-                ex.fail(mcvc_wino43_input_phase_launch(xi, H, W, ex.s));
-                WinoGemmArgs ga{};
-                ga.a = packed + c.off_w43f; ga.a_xi = c.w3f_xi; ga.lda = c.cout_pk;
-                ga.b = ex.wv; ga.b_xi = (long long)K * NTp; ga.ldb = (int)NTp;
-                ga.c = ex.wm; ga.c_xi = (long long)M * NTp; ga.ldc = (int)NTp;
-                ga.M = M; ga.N = (int)NTp; ga.K = K; ga.nxi = 36;
-                ex.fail(mcvc_wino_gemm_launch(ga, ex.s));
-                WinoOutArgs oa{};
-                oa.m = ex.wm; oa.bias = packed + c.off_bias;
-                oa.y = y.p + (long long)b0 * y.sb; oa.y_sb = y.sb; oa.y_sc = y.sc; oa.y_sh = y.sh;
-                oa.N = nb; oa.Cout = M; oa.OH = OH; oa.OW = OW; oa.TH = TH; oa.TW = TW; oa.NT = (int)NT; oa.NTp = (int)NTp;
-                oa.shuffle = 0; oa.YH = OH; oa.YW = OW; oa.accumulate = 0;
-                if (ex.fuse_next && nbc == NB) { ex.pend = oa; ex.pend_pts = 43; }
-                else ex.fail(mcvc_wino43_output_launch(oa, ex.s));
-            }
-            return;
-        }
-    }
-    if (c.wino3 && wino_enabled() && ex.wv && !shuffle && (H & 1) == 0 && (W & 1) == 0 && (c.cout_tot % 128) == 0) {
-        // stride-2 5x5 forward = 3x3 stride-1 conv over the four input phases: Winograd F(2x2,3x3), K = 4*Cin
-        static const int en = mcvc_knob("MCVC_WINO3_FWD", 1);
-        const int OH = H / 2, OW = W / 2, K = 4 * c.Cin, M = c.cout_tot;
-        const int TH = (OH + 1) / 2, TW = (OW + 1) / 2;
-        const int nbc = wino_chunk(NB, (long long)TH * TW);
-        const long long NTc = wino_chunk_tiles(NB, (long long)TH * TW);
-        if (en && nbc && NTc >= 64 && 16LL * (K > M ? K : M) * NTc <= ex.wino_cap) {
-            if (nsplit) *nsplit = 1;
-            if (ex.dry) return;
-            for (int b0 = 0; b0 < NB; b0 += nbc) {
-                const int nb = NB - b0 < nbc ? NB - b0 : nbc;
-                const long long NT = (long long)nb * TH * TW, NTp = (NT + 31) & ~31LL;
-                WinoXformArgs xi{};
-                xi.x = x.p + (long long)b0 * x.sb; xi.x_sb = x.sb; xi.x_sc = x.sc; xi.x_sh = x.sh; xi.v = ex.wv;
-                xi.N = nb; xi.C = K; xi.H = OH; xi.W = OW; xi.TH = TH; xi.TW = TW; xi.NT = (int)NT; xi.NTp = (int)NTp; xi.pad = 1;
-                ex.fail(mcvc_wino3_input_phase_launch(xi, H, W, ex.s));
-                WinoGemmArgs ga{};
-                ga.a = packed + c.off_w3f; ga.a_xi = c.w3f_xi; ga.lda = c.cout_pk;
-                ga.b = ex.wv; ga.b_xi = (long long)K * NTp; ga.ldb = (int)NTp;
-                ga.c = ex.wm; ga.c_xi = (long long)M * NTp; ga.ldc = (int)NTp;
-                ga.M = M; ga.N = (int)NTp; ga.K = K; ga.nxi = 16;
-                ex.fail(mcvc_wino_gemm_launch(ga, ex.s));
-                WinoOutArgs oa{};
-                oa.m = ex.wm; oa.bias = packed + c.off_bias;
-                oa.y = y.p + (long long)b0 * y.sb; oa.y_sb = y.sb; oa.y_sc = y.sc; oa.y_sh = y.sh;
-                oa.N = nb; oa.Cout = M; oa.OH = OH; oa.OW = OW; oa.TH = TH; oa.TW = TW; oa.NT = (int)NT; oa.NTp = (int)NTp;
-                oa.shuffle = 0; oa.YH = OH; oa.YW = OW; oa.accumulate = 0;
-                if (ex.fuse_next && nbc == NB) { ex.pend = oa; ex.pend_pts = 16; }
-                else ex.fail(mcvc_wino3_output_launch(oa, ex.s));
-            }
-            return;
-        }
-    }
-    if (!ex.dry && (((ex.pack_skips & 1) && c.off_tk >= 0) || ((ex.pack_skips & 2) && (c.wino || c.wino3)))) { ex.fail(MCVC_ERR_INVALID); return; }
+    if (conv_wino(ex, c, packed, 0, NB, H, W, x, y, shuffle, 0) || (!shuffle && conv_wino3(ex, c, packed, 0, NB, H, W, x, y, 0))) { if (nsplit) *nsplit = 1; return; }
+    if (stale_direct(ex, c)) return;
     ConvProblem p{c.Cin, H, W, c.cout_tot, conv_out(H, c.KH, c.stride, c.ph), conv_out(W, c.KW, c.stride, c.pw),
                   c.KH, c.KW, c.stride, c.ph, c.pw};
     ConvIO io{};
@@ -734,72 +798,8 @@ static void conv_dgrad(Exec& ex, const ConvSpec& c, const float* packed, int NB,
         ex.fail(mcvc_igemm_launch(g, ex.s));
         return;
     }
-    if (c.wino3 && wino_enabled() && ex.wv && wino43_applies(ex, c, NB, OH, OW) && 2 * OH == H && 2 * OW == W) {
-        // ... as F(4x4,3x3)
-        static const int en = mcvc_knob("MCVC_WINO3", 1);
-        const int K = c.cout_tot, M = 4 * c.Cin;
-        const int TH = OH / 4, TW = OW / 4;
-        const int nbc = wino4_chunk(ex, NB, (long long)TH * TW, K > M ? K : M, 36);
-        if (en && nbc && ((long long)nbc * TH * TW >= 64 || ex.force_scheme == 2) && (M % 128) == 0 && (K % 16) == 0) {
-            if (nsplit) *nsplit = 1;
-            if (ex.dry) return;
-            for (int b0 = 0; b0 < NB; b0 += nbc) {
-                const int nb = NB - b0 < nbc ? NB - b0 : nbc;
-                const long long NT = (long long)nb * TH * TW, NTp = (NT + 31) & ~31LL;
-                WinoXformArgs xi{};
-                xi.x = dy.p + (long long)b0 * dy.sb; xi.x_sb = dy.sb; xi.x_sc = dy.sc; xi.x_sh = dy.sh; xi.v = ex.wv;
-                xi.N = nb; xi.C = K; xi.H = OH; xi.W = OW; xi.TH = TH; xi.TW = TW; xi.NT = (int)NT; xi.NTp = (int)NTp; xi.pad = 1;
-                ex.fail(mcvc_wino43_input_launch(xi, ex.s));
-                WinoGemmArgs ga{};
-                ga.a = packed + c.off_w43; ga.a_xi = c.w3_xi; ga.lda = c.mg_ld;
-                ga.b = ex.wv; ga.b_xi = (long long)K * NTp; ga.ldb = (int)NTp;
-                ga.c = ex.wm; ga.c_xi = (long long)M * NTp; ga.ldc = (int)NTp;
-                ga.M = M; ga.N = (int)NTp; ga.K = K; ga.nxi = 36;
-                ex.fail(mcvc_wino_gemm_launch(ga, ex.s));
-                WinoOutArgs oa{};
-                oa.m = ex.wm; oa.bias = nullptr;
-                oa.y = dx.p + (long long)b0 * dx.sb; oa.y_sb = dx.sb; oa.y_sc = dx.sc; oa.y_sh = dx.sh;
-                oa.N = nb; oa.Cout = M; oa.OH = OH; oa.OW = OW; oa.TH = TH; oa.TW = TW; oa.NT = (int)NT; oa.NTp = (int)NTp;
-                oa.shuffle = 1; oa.YH = H; oa.YW = W; oa.accumulate = accumulate;
-                ex.fail(mcvc_wino43_output_launch(oa, ex.s));
-            }
-            return;
-        }
-    }
-    if (c.wino3 && wino_enabled() && ex.wv) {
-        // merged stride-2 data-gradient = a 3x3 stride-1 conv over dY with 4*Cin output channels: Winograd F(2x2,3x3)
-        static const int en = mcvc_knob("MCVC_WINO3", 1);
-        const int K = c.cout_tot, M = 4 * c.Cin;
-        const int TH = (OH + 1) / 2, TW = (OW + 1) / 2;
-        const int nbc = wino_chunk(NB, (long long)TH * TW);
-        const long long NTc = wino_chunk_tiles(NB, (long long)TH * TW);
-        if (en && nbc && NTc >= 64 && 16LL * (K > M ? K : M) * NTc <= ex.wino_cap && (H + 1) / 2 == OH && (W + 1) / 2 == OW) {
-            if (nsplit) *nsplit = 1;
-            if (ex.dry) return;
-            for (int b0 = 0; b0 < NB; b0 += nbc) {
-                const int nb = NB - b0 < nbc ? NB - b0 : nbc;
-                const long long NT = (long long)nb * TH * TW, NTp = (NT + 31) & ~31LL;
-                WinoXformArgs xi{};
-                xi.x = dy.p + (long long)b0 * dy.sb; xi.x_sb = dy.sb; xi.x_sc = dy.sc; xi.x_sh = dy.sh; xi.v = ex.wv;
-                xi.N = nb; xi.C = K; xi.H = OH; xi.W = OW; xi.TH = TH; xi.TW = TW; xi.NT = (int)NT; xi.NTp = (int)NTp; xi.pad = 1;
-                ex.fail(mcvc_wino3_input_launch(xi, ex.s));
-                WinoGemmArgs ga{};
-                ga.a = packed + c.off_w3; ga.a_xi = c.w3_xi; ga.lda = c.mg_ld;
-                ga.b = ex.wv; ga.b_xi = (long long)K * NTp; ga.ldb = (int)NTp;
-                ga.c = ex.wm; ga.c_xi = (long long)M * NTp; ga.ldc = (int)NTp;
-                ga.M = M; ga.N = (int)NTp; ga.K = K; ga.nxi = 16;
-                ex.fail(mcvc_wino_gemm_launch(ga, ex.s));
-                WinoOutArgs oa{};
-                oa.m = ex.wm; oa.bias = nullptr;
-                oa.y = dx.p + (long long)b0 * dx.sb; oa.y_sb = dx.sb; oa.y_sc = dx.sc; oa.y_sh = dx.sh;
-                oa.N = nb; oa.Cout = M; oa.OH = OH; oa.OW = OW; oa.TH = TH; oa.TW = TW; oa.NT = (int)NT; oa.NTp = (int)NTp;
-                oa.shuffle = 1; oa.YH = H; oa.YW = W; oa.accumulate = accumulate;
-                ex.fail(mcvc_wino3_output_launch(oa, ex.s));
-            }
-            return;
-        }
-    }
-    if (!ex.dry && (((ex.pack_skips & 1) && c.off_tk >= 0) || ((ex.pack_skips & 2) && (c.wino || c.wino3)))) { ex.fail(MCVC_ERR_INVALID); return; }
+    if (conv_wino3(ex, c, packed, 1, NB, H, W, dy, dx, accumulate)) { if (nsplit) *nsplit = 1; return; }
+    if (stale_direct(ex, c)) return;
     if (!ex.dry && (ex.pack_skips & 8) && c.stride == 2) { ex.fail(MCVC_ERR_INVALID); return; }      // (mcvc_disc_pack_small: these copies are stale)
     static const int ucls_nb = mcvc_knob("MCVC_DGRAD_CLASSES_NB", 8);
     const bool per_class = c.merged && c.off_dcls >= 0 && NB >= ucls_nb;
@@ -900,14 +900,8 @@ static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, int NB,
         g.a = dy.p; g.a_cs = dy.sc; g.a_sn = dy.sb; g.a_pitch = dy.sh;
         g.b = x.p; g.b_cs = x.sc; g.b_sn = x.sb; g.ntaps = wtaps;
         if (ig3) {
-            const int pw = mcvc_xs_pw(W);
-            const long long plane = mcvc_xs_plane(H, W);
-            g.b_pitch = pw;
-            for (int kh = 0; kh < 3; ++kh)
-                for (int kw = 0; kw < 3; ++kw) {          // tap (kh, kw) of output (oh, ow) multiplies x[2 oh + kh - 1][2 ow + kw - 1]  (conv_fwd_igemm)
-                    const int ph = (kh == 1) ? 0 : 1, di = (kh == 0) ? -1 : 0, pq = (kw == 1) ? 0 : 1, dj = (kw == 0) ? -1 : 0;
-                    g.boff[3 * kh + kw] = (long long)(2 * ph + pq) * plane + (long long)(1 + di) * pw + 4 + dj;
-                }
+            g.b_pitch = mcvc_xs_pw(W);
+            xs_tap_offsets(H, W, g.boff);
         } else {                                          // 1 x KW over dense rows: tap kw multiplies x[w + kw - pw]; the rows' ends count as padding
             g.b_pitch = x.sh; g.zw = (c.KW == 3) ? W : 0;
             for (int kw = 0; kw < c.KW; ++kw) g.boff[kw] = kw - c.pw;
@@ -926,125 +920,19 @@ static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, int NB,
         done = true;
     }
     if (!done && ex.wgrad_x_xs) { ex.fail(MCVC_ERR_WORKSPACE); return; }     // (nothing else reads a phase-split input: never fall through to a dense reader)
-    if (!done && wino_enabled() && ex.wu && c.nbr == 1 && grads[c.wi[0]] && wino4_applies(ex, c, NB, H, W) && (c.Cout % 128) == 0 && (c.Cin % 64) == 0 &&
-        64LL * c.Cout * c.Cin <= ex.wu_cap) {
-        // F(4x4,5x5) weight gradient: the same three steps on 8x8 tiles and 64 points
-        const int TH = H / 4, TW = W / 4;
-        const int nbc = wino4_chunk(ex, NB, (long long)TH * TW, c.Cout > c.Cin ? c.Cout : c.Cin);
-        if (nbc && ((long long)nbc * TH * TW >= 32 || ex.force_scheme == 2)) {
-            for (int b0 = 0; b0 < NB; b0 += nbc) {
-                const int nb = NB - b0 < nbc ? NB - b0 : nbc;
-                const long long NT = (long long)nb * TH * TW, NTp = (NT + 31) & ~31LL;
-                WinoXformArgs xi{};
-                xi.x = x.p + (long long)b0 * x.sb; xi.x_sb = x.sb; xi.x_sc = x.sc; xi.x_sh = x.sh; xi.v = ex.wv2;
-                xi.N = nb; xi.C = c.Cin; xi.H = H; xi.W = W; xi.TH = TH; xi.TW = TW; xi.NT = (int)NT; xi.NTp = (int)NTp; xi.pad = 2;
-                ex.fail(mcvc_wino4_input_t_launch(xi, ws));
-                WinoXformArgs di{};
-                di.x = dy.p + (long long)b0 * dy.sb; di.x_sb = dy.sb; di.x_sc = dy.sc; di.x_sh = dy.sh; di.v = ex.wm2;
-                di.N = nb; di.C = c.Cout; di.H = H; di.W = W; di.TH = TH; di.TW = TW; di.NT = (int)NT; di.NTp = (int)NTp; di.pad = 0;
-                ex.fail(mcvc_wino4_dy_t_launch(di, ws));
-                WinoGemmArgs ga{};
-                ga.a = ex.wm2; ga.a_xi = NTp * c.Cout; ga.lda = c.Cout;
-                ga.b = ex.wv2; ga.b_xi = NTp * c.Cin; ga.ldb = c.Cin;
-                ga.c = ex.wu; ga.c_xi = (long long)c.Cout * c.Cin; ga.ldc = c.Cin;
-                ga.M = c.Cout; ga.N = c.Cin; ga.K = (int)((NT + 15) & ~15LL);      /* (rows [NT, NTp) of the tile-major operands are zeros: contract over the 16-row stages that hold tiles -- 80 instead of 96 at one sample) */ ga.nxi = 64;
-                ex.fail(mcvc_wino_gemm_launch(ga, ws));
-                ex.fail(mcvc_wino4_dw_launch(ex.wu, grads[c.wi[0]], c.Cout, c.Cin, ws));
-            }
-            done = true;
-        }
-    }
-    if (!done && c.wino && wino_enabled() && ex.wu && c.nbr == 1 && grads[c.wi[0]]) {
-        // Winograd weight gradient: dU[xi] = dM[xi] V[xi]^T over the tiles, then dW += G^T dU G.  Operands tile-major.
-        static const int en = mcvc_knob("MCVC_WINO_WGRAD", 1);
-        const int TH = (H + 1) / 2, TW = (W + 1) / 2;
-        const int nbc = wino_chunk(NB, (long long)TH * TW);
-        const long long NTc = wino_chunk_tiles(NB, (long long)TH * TW);
-        if (en && nbc && (c.Cout % 128) == 0 && (c.Cin % 64) == 0 && 36LL * NTc * c.Cout <= ex.wino_cap && 36LL * NTc * c.Cin <= ex.wino_cap &&
-            36LL * c.Cout * c.Cin <= ex.wu_cap) {
-            for (int b0 = 0; b0 < NB; b0 += nbc) {
-                const int nb = NB - b0 < nbc ? NB - b0 : nbc;
-                const long long NT = (long long)nb * TH * TW, NTp = (NT + 31) & ~31LL;
-                WinoXformArgs xi{};
-                xi.x = x.p + (long long)b0 * x.sb; xi.x_sb = x.sb; xi.x_sc = x.sc; xi.x_sh = x.sh; xi.v = ex.wv2;
-                xi.N = nb; xi.C = c.Cin; xi.H = H; xi.W = W; xi.TH = TH; xi.TW = TW; xi.NT = (int)NT; xi.NTp = (int)NTp; xi.pad = 2;
-                ex.fail(mcvc_wino_input_t_launch(xi, ws));
-                WinoXformArgs di{};
-                di.x = dy.p + (long long)b0 * dy.sb; di.x_sb = dy.sb; di.x_sc = dy.sc; di.x_sh = dy.sh; di.v = ex.wm2;
-                di.N = nb; di.C = c.Cout; di.H = H; di.W = W; di.TH = TH; di.TW = TW; di.NT = (int)NT; di.NTp = (int)NTp; di.pad = 0;
-                ex.fail(mcvc_wino_dy_t_launch(di, ws));
-                WinoGemmArgs ga{};
-                ga.a = ex.wm2; ga.a_xi = NTp * c.Cout; ga.lda = c.Cout;          // dMt[xi][tile][co]
-                ga.b = ex.wv2; ga.b_xi = NTp * c.Cin; ga.ldb = c.Cin;            // Vt[xi][tile][ci]
-                ga.c = ex.wu; ga.c_xi = (long long)c.Cout * c.Cin; ga.ldc = c.Cin;
-                ga.M = c.Cout; ga.N = c.Cin; ga.K = (int)((NT + 15) & ~15LL);      /* (rows [NT, NTp) of the tile-major operands are zeros: contract over the 16-row stages that hold tiles -- 80 instead of 96 at one sample) */
-                ex.fail(mcvc_wino_gemm_launch(ga, ws));
-                ex.fail(mcvc_wino_dw_launch(ex.wu, grads[c.wi[0]], c.Cout, c.Cin, ws));      // dW += G^T dU G: the chunks add up
-            }
-            done = true;
-        }
-    }
-    if (!done && c.wino3 && wino_enabled() && ex.wu && (H & 1) == 0 && (W & 1) == 0 && grads[c.wi[0]] && (c.nbr == 1 || grads[c.wi[1]]) &&
-        wino43_applies(ex, c, NB, OH, OW)) {
-        // ... as F(4x4,3x3)
-        static const int en = mcvc_knob("MCVC_WINO3_WGRAD", 1);
-        const int K4 = 4 * c.Cin, M = c.cout_tot;
-        const int TH = OH / 4, TW = OW / 4;
-        const int nbc = wino4_chunk(ex, NB, (long long)TH * TW, M > K4 ? M : K4, 36);
-        if (en && nbc && ((long long)nbc * TH * TW >= 32 || ex.force_scheme == 2) && (M % 128) == 0 && (K4 % 64) == 0 && 36LL * M * K4 <= ex.wu_cap) {
-            for (int b0 = 0; b0 < NB; b0 += nbc) {
-                const int nb = NB - b0 < nbc ? NB - b0 : nbc;
-                const long long NT = (long long)nb * TH * TW, NTp = (NT + 31) & ~31LL;
-                WinoXformArgs xi{};
-                xi.x = x.p + (long long)b0 * x.sb; xi.x_sb = x.sb; xi.x_sc = x.sc; xi.x_sh = x.sh; xi.v = ex.wv2;
-                xi.N = nb; xi.C = K4; xi.H = OH; xi.W = OW; xi.TH = TH; xi.TW = TW; xi.NT = (int)NT; xi.NTp = (int)NTp; xi.pad = 1;
-                ex.fail(mcvc_wino43_input_phase_t_launch(xi, H, W, ws));
-                WinoXformArgs di{};
-                di.x = dy.p + (long long)b0 * dy.sb; di.x_sb = dy.sb; di.x_sc = dy.sc; di.x_sh = dy.sh; di.v = ex.wm2;
-                di.N = nb; di.C = M; di.H = OH; di.W = OW; di.TH = TH; di.TW = TW; di.NT = (int)NT; di.NTp = (int)NTp; di.pad = 0;
-                ex.fail(mcvc_wino43_dy_t_launch(di, ws));
-                WinoGemmArgs ga{};
-                ga.a = ex.wm2; ga.a_xi = NTp * M; ga.lda = M;
-                ga.b = ex.wv2; ga.b_xi = NTp * K4; ga.ldb = K4;
-                ga.c = ex.wu; ga.c_xi = (long long)M * K4; ga.ldc = K4;
-                ga.M = M; ga.N = K4; ga.K = (int)((NT + 15) & ~15LL);      /* (rows [NT, NTp) of the tile-major operands are zeros: contract over the 16-row stages that hold tiles -- 80 instead of 96 at one sample) */ ga.nxi = 36;
-                ex.fail(mcvc_wino_gemm_launch(ga, ws));
-                ex.fail(mcvc_wino43_dw_launch(ex.wu, grads[c.wi[0]], c.nbr == 2 ? grads[c.wi[1]] : nullptr, c.Cout, c.nbr, c.Cin, ws));
-            }
-            done = true;
-        }
-    }
-    if (!done && c.wino3 && wino_enabled() && ex.wu && (H & 1) == 0 && (W & 1) == 0 && grads[c.wi[0]] && (c.nbr == 1 || grads[c.wi[1]])) {
-        // stride-2 5x5 weight gradient in the phase formulation (see conv_fwd): dU[xi][co][4ci+2p+q] over the tiles, both
-        // branches (value | gate) in one product, then the 3x3 blocks are scattered back into the two 5x5 gradients
-        static const int en = mcvc_knob("MCVC_WINO3_WGRAD", 1);
-        const int K4 = 4 * c.Cin, M = c.cout_tot;
-        const int TH = (OH + 1) / 2, TW = (OW + 1) / 2;
-        const int nbc = wino_chunk(NB, (long long)TH * TW);
-        const long long NTc = wino_chunk_tiles(NB, (long long)TH * TW);
-        if (en && nbc && (M % 128) == 0 && (K4 % 64) == 0 && 16LL * NTc * M <= ex.wino_cap && 16LL * NTc * K4 <= ex.wino_cap &&
-            16LL * M * K4 <= ex.wu_cap) {
-            for (int b0 = 0; b0 < NB; b0 += nbc) {
-                const int nb = NB - b0 < nbc ? NB - b0 : nbc;
-                const long long NT = (long long)nb * TH * TW, NTp = (NT + 31) & ~31LL;
-                WinoXformArgs xi{};
-                xi.x = x.p + (long long)b0 * x.sb; xi.x_sb = x.sb; xi.x_sc = x.sc; xi.x_sh = x.sh; xi.v = ex.wv2;
-                xi.N = nb; xi.C = K4; xi.H = OH; xi.W = OW; xi.TH = TH; xi.TW = TW; xi.NT = (int)NT; xi.NTp = (int)NTp; xi.pad = 1;
-                ex.fail(mcvc_wino3_input_phase_t_launch(xi, H, W, ws));
-                WinoXformArgs di{};
-                di.x = dy.p + (long long)b0 * dy.sb; di.x_sb = dy.sb; di.x_sc = dy.sc; di.x_sh = dy.sh; di.v = ex.wm2;
-                di.N = nb; di.C = M; di.H = OH; di.W = OW; di.TH = TH; di.TW = TW; di.NT = (int)NT; di.NTp = (int)NTp; di.pad = 0;
-                ex.fail(mcvc_wino3_dy_t_launch(di, ws));
-                WinoGemmArgs ga{};
-                ga.a = ex.wm2; ga.a_xi = NTp * M; ga.lda = M;
-                ga.b = ex.wv2; ga.b_xi = NTp * K4; ga.ldb = K4;
-                ga.c = ex.wu; ga.c_xi = (long long)M * K4; ga.ldc = K4;
-                ga.M = M; ga.N = K4; ga.K = (int)((NT + 15) & ~15LL);      /* (rows [NT, NTp) of the tile-major operands are zeros: contract over the 16-row stages that hold tiles -- 80 instead of 96 at one sample) */ ga.nxi = 16;
-                ex.fail(mcvc_wino_gemm_launch(ga, ws));
-                ex.fail(mcvc_wino3_dw_launch(ex.wu, grads[c.wi[0]], c.nbr == 2 ? grads[c.wi[1]] : nullptr, c.Cout, c.nbr, c.Cin, ws));
-            }
-            done = true;
-        }
+    if (!done && (c.wino ? c.nbr == 1 : c.wino3 && (H & 1) == 0 && (W & 1) == 0 && (c.nbr == 1 || grads[c.wi[1]])) && wino_enabled() && ex.wu && grads[c.wi[0]]) {
+        // Winograd weight gradient (wino_wgrad_pass); the stride-2 layers' 3x3 convolution runs over the phase planes, OH x OW
+        static const int en25 = mcvc_knob("MCVC_WINO_WGRAD", 1), en3 = mcvc_knob("MCVC_WINO3_WGRAD", 1);
+        const int IH = c.wino ? H : OH, IW = c.wino ? W : OW, N = c.wino ? c.Cin : 4 * c.Cin, M = c.cout_tot;
+        auto attempt = [&](const WinoFam& f, int en, int min_tiles) {
+            if (!en || (M % 128) != 0 || (N % 64) != 0 || (long long)f.pts * M * N > ex.wu_cap) return false;
+            const int nbc = wino_nbc(ex, f, NB, wino_tiles(f, IH, IW), M > N ? M : N, min_tiles);
+            if (nbc) wino_wgrad_pass(ex, f, c, grads, NB, nbc, H, W, x, dy, ws);
+            return nbc != 0;
+        };
+        // (MCVC_WINO_WGRAD switches the 36-point form only)
+        if (c.wino) done = (wino4_applies(ex, c, NB, H, W) && attempt(kWino[kF45], 1, 32)) || attempt(kWino[kF25], en25, 0);
+        else done = (wino43_applies(ex, c, NB, OH, OW) && attempt(kWino[kF43], en3, 32)) || attempt(kWino[kF23], en3, 0);
     }
     if (!done && c.cout_tot == 1 && mcvc_wgrad_cout1_applies(p) && grads[c.wi[0]]) {       // one output channel: VALU kernel
         WgradIO io{x.p, x.sb, x.sc, x.sh, dy.p, dy.sb, dy.sc, dy.sh};
@@ -1482,12 +1370,11 @@ static void norm_fwd(Exec& ex, float* x, long long x_sn, long long x_sc, long lo
     a.stats = stats; a.y = y; a.res = res; a.y_sn = y_sn; a.y_sc = y_sc; a.y_sh = y_sh;
     a.N = N; a.C = C; a.H = H; a.W = W; a.act = act; a.eps = kInEps;
     if (ex.y_xs_pw) { a.y_xs = 1; a.xs_pw = ex.y_xs_pw; a.xs_plane = ex.y_xs_plane; ex.y_xs_pw = 0; }
-    if (ex.pend_pts) {
-        const int pts = ex.pend_pts;
-        ex.pend_pts = 0;
-        if (mcvc_norm_fwd_wino_applies(a, ex.pend, pts)) { ex.fail(mcvc_norm_fwd_wino_launch(a, ex.pend, pts, ex.s)); return; }
-        ex.fail(pts == 16 ? mcvc_wino3_output_launch(ex.pend, ex.s) : pts == 36 ? mcvc_wino_output_launch(ex.pend, ex.s)
-                : pts == 43 ? mcvc_wino43_output_launch(ex.pend, ex.s) : mcvc_wino4_output_launch(ex.pend, ex.s));
+    if (ex.pend_fam) {
+        const WinoFam& f = *ex.pend_fam;
+        ex.pend_fam = nullptr;
+        if (mcvc_norm_fwd_wino_applies(a, ex.pend, f.norm_pts)) { ex.fail(mcvc_norm_fwd_wino_launch(a, ex.pend, f.norm_pts, ex.s)); return; }
+        ex.fail(f.output(ex.pend, ex.s));
     }
     ex.fail(mcvc_norm_fwd_launch(a, ex.s));
 }
