@@ -404,7 +404,12 @@ int mcvc_conv2d_wgrad(const float* x, const float* dy, float* dw, float* slabs, 
  *      with 4x4 output tiles (sample / tile thresholds lifted; image sides must be multiples of 4 -- 8 for the stride-2 layers),
  *      3 no Winograd (direct kernels for these layers since r5), 4 direct kernels only, 5 implicit GEMM (forward / dgrad / wgrad of the 3x3
  *      stride-2 layers: the kernels the discriminator passes run, sgemm.h; the dense operand is converted to their layout first).  w0 / w1 = the OIHW tensors themselves (the
- *      pre-r5 staged data gradient multiplied them in place; unused now).  pixel_shuffle: the forward store of the up-sampling layers (model.py:232).   */
+ *      pre-r5 staged data gradient multiplied them in place; unused now).  pixel_shuffle: the forward store of the up-sampling layers (model.py:232).
+ *      Schemes 1 / 2 and the tile count (a Winograd pass keeps at most 16384 tiles in its workspaces): a batch with more 2x2 tiles runs as
+ *      several passes over equal chunks of samples (3 samples of 5550 tiles: 2 + 1), weight gradients adding up over the chunks.  ONE sample of
+ *      exactly 16384 tiles (a 256 x 256 image of a stride-1 layer) still runs Winograd; one with more (258 x 256: 16512 tiles) is not refused:
+ *      the scheme is declined without an error and forward, data gradient and weight gradient run on the direct kernels, with the same
+ *      results to rounding (tests/test_hip_wino_chunks.py tells the two apart by the launch trace).   */
 long long mcvc_layer_packed_floats(int Cin, int Cout, int branches, int KH, int KW, int stride, int pad_h, int pad_w);
 long long mcvc_layer_scratch_floats(int N, int H, int W, int Cin, int Cout, int branches, int KH, int KW, int stride, int pad_h, int pad_w);
 int mcvc_layer_pack(const float* w0, const float* b0, const float* w1, const float* b1, float* packed, int Cin, int Cout, int branches,

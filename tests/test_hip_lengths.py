@@ -227,3 +227,76 @@ def test_inference_cli_at_utterance_lengths(tmp_path, gp64):
         for i, (T, ref, spread) in enumerate(zip(CLI_LENGTHS, refs, spreads)):
             got = (np.load(os.path.join(out, "%d-converted_SPKA_to_SPKB.npy" % i)).astype(np.float64) - mean) / std
             check("CLI utterance %d T=%d" % (i, T), dtype, got[None], ref[None], spread[dtype])
+
+
+def _wino_gemm_launches(fn):
+    from test_hip_model import _launches
+    return _launches("wino_gemm", fn)
+
+
+def test_generator_batch_of_five_long_utterances_runs_chunked_winograd_passes(gen, gp64):
+    """bs 5 at T = 660 (T/4 = 165, odd): upSample2 and downSample1 have 20 x 165 = 3300 2x2 tiles per sample and no 4x4 form (330 columns), so
+    their Winograd passes hold 16384 / 3300 = 4 samples at most and run as chunks of 3 + 2 samples -- forward, data gradient and weight
+    gradient.  Every sample of infer f32 and of the autograd forward vs its own bs-1 result; samples 0 and 4 (one of each chunk) vs the fp64
+    oracle; with a seeded dout the batch's parameter gradients and dx vs the sum, respectively the stack, of the five bs-1 backward passes
+    (1e-4 of each tensor's norm, the gate of test_backward_over_a_window_of_the_forward_samples; the conv biases in front of an InstanceNorm,
+    whose gradient is rounding noise below 1e-4, are skipped).  The launch trace proves the regime: the batch's forward makes more Winograd
+    GEMM launches (6: two layers in two chunks) than a bs-1 forward of the same length (4)."""
+    B, T = 5, 660
+    x = inputs(B, T, 4000 + T)
+    xc = x.cuda()
+    params = gen._plist()
+
+    def run(xs, dout):
+        """infer f32, the autograd forward, and its backward's dx; the parameter gradients accumulate in .grad"""
+        with torch.no_grad():
+            f32 = gen.infer(xs, None, "f32").cpu()
+        xg = xs.clone().requires_grad_(True)
+        fwd = gen(xg, torch.ones_like(xs))
+        fwd.backward(dout)
+        return f32, fwd.detach().cpu(), xg.grad.cpu()
+
+    dout = torch.randn(B, 80, _hip.lib().mcvc_gen_out_frames(T), generator=torch.Generator().manual_seed(4001)).cuda()
+    try:
+        for p in params:
+            p.grad = None
+        b_f32, b_fwd, b_dx = run(xc, dout)
+        b_grads = [p.grad.detach().cpu().double() for p in params]
+        for p in params:
+            p.grad = None
+        single = [run(xc[i:i + 1], dout[i:i + 1]) for i in range(B)]
+        s_grads = [p.grad.detach().cpu().double() for p in params]
+    finally:
+        for p in params:
+            p.grad = None
+
+    assert torch.equal(b_f32, b_fwd), ("infer f32 != forward", float((b_f32 - b_fwd).abs().max()))
+    for name, got, k in (("infer", b_f32, 0), ("forward", b_fwd, 1)):
+        for i in range(B):
+            check("T=%d bs5 %s [%d] vs bs1" % (T, name, i), "f32", got[i:i + 1], single[i][k])
+    for i in (0, B - 1):                                   # one sample of each chunk
+        ref = oracle(gp64, x[i:i + 1])
+        check("T=%d bs5 infer [%d] vs fp64" % (T, i), "f32", b_f32[i:i + 1], ref)
+        check("T=%d bs5 forward [%d] vs fp64" % (T, i), "f32", b_fwd[i:i + 1], ref)
+
+    s_dx = torch.cat([s[2] for s in single], 0).double()
+    e_dx = float((b_dx.double() - s_dx).norm() / s_dx.norm())
+    print("T=%d bs5 backward: dx vs the stacked bs-1 passes %.3e" % (T, e_dx))
+    assert e_dx <= 1e-4, e_dx
+    worst, compared = 0.0, 0
+    names = [n for n, _ in gen.named_parameters()]
+    for i, (a_, b_) in enumerate(zip(b_grads, s_grads)):
+        nb_ = float(b_.norm())
+        if nb_ < 1e-4:                                     # conv biases in front of an InstanceNorm: mathematically zero
+            continue
+        e = float((a_ - b_).norm()) / nb_
+        worst, compared = max(worst, e), compared + 1
+        assert e <= 1e-4, (names[i], e)
+    print("T=%d bs5 backward: %d parameter gradients vs the sum of the bs-1 passes, worst %.3e" % (T, compared, worst))
+    assert compared > 40
+
+    with torch.no_grad():
+        n_batch = _wino_gemm_launches(lambda: gen.infer(xc, None, "f32"))
+        n_single = _wino_gemm_launches(lambda: gen.infer(xc[:1], None, "f32"))
+    print("T=%d Winograd GEMM launches per forward: bs5 %d, bs1 %d" % (T, n_batch, n_single))
+    assert n_batch > n_single > 0, (n_batch, n_single)
