@@ -377,6 +377,35 @@ long long mcvc_gl_workspace_floats(int B, int T);
 int mcvc_gl_decode(const float* in, int in_kind, const float* angles0, const float* tables, float* out, float* workspace,
                    long long workspace_floats, int B, int T, int n_iter, float momentum, void* stream);
 
+/* ---- objective evaluation (new): mel-cepstra from log-mels and batched dynamic time warping (csrc/dtw_kernels.hip; the definitions are in
+ *      mask_cyclegan_vc/metrics.py and INTEGRATION.md).  A feature bank is [K][N] fp32, time-contiguous per row: utterances back to back
+ *      along time with an offset table offs[n + 1]; pair p aligns utterance p of bank x with utterance p of bank y.
+ *        mcvc_dtw_max_frames   the longest utterance a pair may hold (4096: the strip boundary row lives in 32 KB of LDS).
+ *        mcvc_dtw_launches     kernel launches of one run: 1, or 2 with paths (the backtrack is its own launch).
+ *        mcvc_cep_basis_init   HOST buffer [n_cep][80]: rows 1 .. n_cep of the orthonormal DCT-II over the 80 mel bins, computed in float64
+ *                              and rounded once; 1 <= n_cep <= 79.  The caller uploads it (16-byte aligned) once per device.
+ *        mcvc_cep_project      the launch: out [n_cep][n_frames] = basis @ (ln 10 * mel [80][n_frames]); DEVICE pointers.  MCVC_ERR_INVALID:
+ *                              a null or misaligned pointer (mel, out: 4 bytes; basis: 16), n_frames < 1, n_cep outside 1 .. 79.
+ *        mcvc_dtw_plan         HOST offset tables in; HOST table [n_pairs][6] int64 out (table == NULL: sizes only), plus the workspace bytes
+ *                              of a run (0 without paths: no Tx x Ty matrix exists then) and the rows of the path buffer.  Row p of the table:
+ *                              x offset, Tx, y offset, Ty, offset of the pair's direction bytes in the workspace, first row of its path
+ *                              (capacity Tx + Ty - 1 rows; `length` of them are written); the last two are -1 without paths.
+ *                              MCVC_ERR_INVALID: n_pairs < 1, a negative first offset, an utterance of fewer than 1 or more than
+ *                              4096 frames (offsets that do not rise included).
+ *        mcvc_dtw_run          all launches on `stream`; no device allocation.  x, y, table (the plan's, uploaded, 16-byte aligned), cost
+ *                              [n_pairs] fp32, length [n_pairs] int32, path (nullable: no paths) [path rows][2] int32 and workspace (16-byte
+ *                              aligned) are DEVICE pointers; x_offs / y_offs are the HOST tables the plan saw, validated again here.
+ *                              d(i, j) = scale * sqrt(sum_k (x[k][i] - y[k][j])^2).  MCVC_ERR_INVALID: a null or misaligned pointer,
+ *                              K outside 1 .. 80, n_pairs < 1, a NaN scale, tables the plan refuses or that reach beyond x_frames / y_frames;
+ *                              MCVC_ERR_WORKSPACE: workspace null or too small -- nothing is launched.                                  */
+int mcvc_dtw_max_frames(void);
+int mcvc_dtw_launches(int want_path);
+int mcvc_cep_basis_init(int n_cep, float* basis_host);
+int mcvc_cep_project(const float* mel, long long n_frames, const float* basis, int n_cep, float* out, void* stream);
+int mcvc_dtw_plan(const int* x_offs, const int* y_offs, int n_pairs, int want_path, long long* table, long long* workspace_bytes, long long* path_rows);
+int mcvc_dtw_run(const float* x, long long x_frames, const float* y, long long y_frames, int K, float scale, const int* x_offs, const int* y_offs,
+                 const long long* table, int n_pairs, float* cost, int* length, int* path, void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- single-op entry points (kernel parity tests; same kernels the network calls use) ---------- */
 /* y[N,Cout,OH,OW] = conv2d(x[N,Cin,H,W], w[Cout,Cin,KH,KW]) + bias ; stride 1 or 2.
  * wpack: scratch of mcvc_conv2d_pack_floats() floats, zero-initialised by the caller.

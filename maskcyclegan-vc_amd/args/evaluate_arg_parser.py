@@ -1,0 +1,33 @@
+"""Flags of ``python -m mask_cyclegan_vc.evaluate`` (new: the reference has no objective evaluation).  A plain parser: evaluation seeds
+nothing, loads no checkpoint and creates nothing but ``metrics.json`` in the run directory."""
+import argparse
+
+
+class EvaluateArgParser(object):
+    FLAGS = [
+        ("--name", dict(type=str, default="debug", help="Experiment name: the run directory is <save_dir>/<name>, as for mask_cyclegan_vc.test.")),
+        ("--save_dir", dict(type=str, default="/home/results/", help="Directory for results.")),
+        ("--converted_dir", dict(type=str, default=None, help="Folder of <i>-converted_<src>_to_<tgt>.npy files as mask_cyclegan_vc.test writes them "
+                                 "(i: index in the source list).  Default: <save_dir>/<name>/converted_mel.")),
+        ("--preprocessed_data_dir", dict(type=str, default="vcc2018_training_preprocessed/", help="Directory containing preprocessed dataset files.")),
+        ("--target_speaker_id", dict(type=str, default=None, help="References: the target speaker's preprocessed cache, de-normalised with its norm_stat. "
+                                     "Utterance i must be the sentence of converted utterance i (a parallel corpus): that is the caller's contract.")),
+        ("--target_wav_dir", dict(type=str, default=None, help="References: the sorted .wav files of this folder through the GPU front-end "
+                                  "(data_preprocessing/audio2mel.py).  File i must be the sentence of converted utterance i.")),
+        ("--source_speaker_id", dict(type=str, default=None, help="Also report the unconverted baseline: the source speaker's preprocessed utterances "
+                                     "against the same references.")),
+        ("--n_cep", dict(type=int, default=24, help="Mel-cepstral coefficients c_1 .. c_n_cep (1 .. 79) from the 80-band log-mel.")),
+    ]
+
+    def __init__(self):
+        self.parser = argparse.ArgumentParser(description=type(self).__name__)
+        for flag, kw in self.FLAGS:
+            self.parser.add_argument(flag, **kw)
+
+    def parse_args(self, argv=None):
+        args = self.parser.parse_args(argv)
+        if (args.target_speaker_id is None) == (args.target_wav_dir is None):
+            self.parser.error("give the references as exactly one of --target_speaker_id and --target_wav_dir")
+        if not 1 <= args.n_cep <= 79:
+            self.parser.error("--n_cep takes a number of coefficients in 1 .. 79")
+        return args

@@ -25,6 +25,7 @@
 #include "audio.h"
 #include "vocoder.h"
 #include "griffinlim.h"
+#include "dtw.h"
 #include "../../include/mcvc.h"
 #include <string.h>
 #include <algorithm>
@@ -2637,6 +2638,34 @@ int mcvc_gl_decode(const float* in, int in_kind, const float* angles0, const flo
                    long long workspace_floats, int B, int T, int n_iter, float momentum, void* stream)
 {
     return mcvc_gl_decode_launch(in, in_kind, angles0, tables, out, workspace, workspace_floats, B, T, n_iter, momentum, (hipStream_t)stream);
+}
+
+// ---- objective evaluation: mel-cepstra and batched DTW (dtw_kernels.hip) ----
+int mcvc_dtw_max_frames(void) { return MCVC_DTW_MAX_FRAMES; }
+
+int mcvc_dtw_launches(int want_path) { return want_path ? 2 : 1; }
+
+int mcvc_cep_basis_init(int n_cep, float* basis_host)
+{
+    if (!basis_host || ((uintptr_t)basis_host & 3)) return MCVC_ERR_INVALID;
+    return mcvc_cep_basis_fill(n_cep, basis_host);
+}
+
+int mcvc_cep_project(const float* mel, long long n_frames, const float* basis, int n_cep, float* out, void* stream)
+{
+    return mcvc_cep_project_launch(mel, n_frames, basis, n_cep, out, (hipStream_t)stream);
+}
+
+int mcvc_dtw_plan(const int* x_offs, const int* y_offs, int n_pairs, int want_path, long long* table, long long* ws_bytes, long long* path_rows)
+{
+    return mcvc_dtw_plan_host(x_offs, y_offs, n_pairs, want_path, table, ws_bytes, path_rows);
+}
+
+int mcvc_dtw_run(const float* x, long long x_frames, const float* y, long long y_frames, int K, float scale, const int* x_offs, const int* y_offs,
+                 const long long* table, int n_pairs, float* cost, int* length, int* path, void* workspace, long long workspace_bytes, void* stream)
+{
+    return mcvc_dtw_run_launch(x, x_frames, y, y_frames, K, scale, x_offs, y_offs, table, n_pairs, cost, length, path, workspace, workspace_bytes,
+                               (hipStream_t)stream);
 }
 
 int mcvc_axpy(float* y, const float* x, float alpha, long long n, void* stream)

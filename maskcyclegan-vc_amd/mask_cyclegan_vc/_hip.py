@@ -114,6 +114,13 @@ _SIGS = {
     "mcvc_gl_tables_init": (c_int, [c_void_p, c_void_p]),
     "mcvc_gl_workspace_floats": (c_longlong, [c_int, c_int]),
     "mcvc_gl_decode": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_float, c_void_p]),
+    "mcvc_dtw_max_frames": (c_int, []),
+    "mcvc_dtw_launches": (c_int, [c_int]),
+    "mcvc_cep_basis_init": (c_int, [c_int, c_void_p]),
+    "mcvc_cep_project": (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_void_p]),
+    "mcvc_dtw_plan": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.POINTER(c_longlong), ctypes.POINTER(c_longlong)]),
+    "mcvc_dtw_run": (c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_longlong, c_void_p]),
     "mcvc_axpy": (c_int, [c_void_p, c_void_p, c_float, c_longlong, c_void_p]),
     "mcvc_conv2d_pack_floats": (c_longlong, [c_int, c_int, c_int, c_int]),
     "mcvc_conv2d_forward": (c_int, [c_void_p] * 6 + [c_int] * 12 + [c_void_p]),

@@ -1,0 +1,195 @@
+"""Objective evaluation on the HIP kernels: batched dynamic time warping and mel-cepstral distortion (csrc/dtw_kernels.hip through
+``mcvc_cep_project`` and ``mcvc_dtw_run``).  All arithmetic runs in the kernels; Python builds tables and moves data.  There is no CPU path.
+
+* ``dtw(x, y, scale=1.0, return_path=False)``   ragged batch of pairs -> cost [n], length [n] (and the warping paths);
+* ``mel_cepstra(mels, n_cep=24)``               log10-mels [80, T_i] -> cepstra bank ([n_cep, N], offsets);
+* ``mcd(converted_mels, target_mels, n_cep=24)`` -> per-pair dB, path lengths and the mean.
+
+Definitions (tests/dtw_checker.py restates them in float64):
+
+Features.  A bank is [K, N] float32, time-contiguous per row: utterances concatenated along time, with frame offsets offs[n + 1];
+1 <= K <= 80.  ``x`` / ``y`` are lists of [K, T_i] tensors or arrays, or ``(bank, offs)`` pairs already on the device.
+
+Cepstra from the project's log10-mels [80, T]:  c[k, t] = sum_m B[k, m] * ln(10) * mel[m, t] for k = 1 .. n_cep, B the orthonormal DCT-II
+over the 80 mel bins (B[k, m] = sqrt(2 / 80) cos(pi (m + 1/2) k / 80)); c_0, the energy term, is dropped.  The basis is computed in float64
+on the host, rounded once and uploaded once per device.
+
+Frame distance.  d(i, j) = scale * sqrt(sum_k (x[k, i] - y[k, j])^2), computed from differences.  For MCD, scale = (10 / ln 10) sqrt(2): dB.
+
+DTW.  acc(0, 0) = d(0, 0); acc(i, j) = d(i, j) + min over the existing predecessors (i-1, j-1), (i-1, j), (i, j-1), taken in that order
+and replaced only on strict <; len(i, j) = len(chosen predecessor) + 1 with len(0, 0) = 1.  Per pair cost = acc(Tx-1, Ty-1) and
+length = len(Tx-1, Ty-1); on request the path as int32 [length, 2] from (0, 0) to (Tx-1, Ty-1).  MCD = cost / length: the mean over the
+warping path that espnet-style evaluation scripts report.
+
+Comparability.  These cepstra come from an 80-band mel spectrum, NOT from WORLD mel-cepstral coefficients: the numbers compare runs of this
+project with one another (checkpoints, ``--dtype`` settings, decoders), not with the tables of papers.
+
+A batch equals its single calls bit for bit: every pair is one wavefront that sees only its own two utterances.  The default call writes
+no Tx x Ty matrix; ``return_path=True`` stores one direction byte per cell and a second launch walks them back.
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _hip
+
+N_MEL = 80
+MAX_K = 80
+TABLE_COLS = 6
+MCD_SCALE = (10.0 / math.log(10.0)) * math.sqrt(2.0)
+
+_basis = {}                                                            # (device index, n_cep) -> the constant operand, uploaded once
+
+
+def dct_basis(n_cep):
+    """float64 [n_cep, 80]: rows 1 .. n_cep of the orthonormal DCT-II over the 80 mel bins."""
+    n_cep = int(n_cep)
+    if not 1 <= n_cep <= N_MEL - 1:
+        raise ValueError("n_cep must lie in 1 .. %d, got %r" % (N_MEL - 1, n_cep))
+    k = np.arange(1, n_cep + 1, dtype=np.float64)[:, None]
+    m = np.arange(N_MEL, dtype=np.float64)[None, :]
+    return np.sqrt(2.0 / N_MEL) * np.cos(np.pi * (m + 0.5) * k / N_MEL)
+
+
+def host_basis(n_cep):
+    """The projection's constant operand as a float32 host array (``mcvc_cep_basis_init``)."""
+    n_cep = int(n_cep)
+    if not 1 <= n_cep <= N_MEL - 1:
+        raise ValueError("n_cep must lie in 1 .. %d, got %r" % (N_MEL - 1, n_cep))
+    host = np.empty((n_cep, N_MEL), dtype=np.float32)
+    _hip.check(_hip.lib().mcvc_cep_basis_init(n_cep, host.ctypes.data), "mcvc_cep_basis_init")
+    return host
+
+
+def max_frames():
+    return int(_hip.lib().mcvc_dtw_max_frames())
+
+
+def _device(device=None):
+    if not torch.cuda.is_available():
+        raise RuntimeError("mask_cyclegan_vc.metrics (MI355X build) needs a HIP device; there is no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("mask_cyclegan_vc.metrics (MI355X build): device must be a HIP device; there is no CPU path")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+def bank(feats, device=None, rows=None):
+    """list of [K, T_i] (tensors or arrays) or ``(bank, offs)`` -> (float32 device tensor [K, N], int32 numpy offsets [n + 1]).
+    Shapes, finiteness and the device are checked here."""
+    dev = _device(device)
+    if isinstance(feats, tuple) and len(feats) == 2 and isinstance(feats[0], torch.Tensor) and feats[0].dim() == 2 and not isinstance(feats[1], torch.Tensor):
+        b, offs = feats
+        if not b.is_cuda:
+            raise RuntimeError("mask_cyclegan_vc.metrics (MI355X build): tensors must live on a HIP device; there is no CPU path")
+        if b.device != dev:
+            raise RuntimeError("bank on %s, metrics on %s" % (b.device, dev))
+        offs = np.ascontiguousarray(offs, dtype=np.int64).reshape(-1)
+        if offs.size < 2 or offs[0] != 0 or offs[-1] != b.shape[1] or bool((np.diff(offs) < 1).any()):
+            raise ValueError("offsets must rise from 0 to the bank's %d frames" % b.shape[1])
+        b = b.detach().to(torch.float32).contiguous()
+    else:
+        items = list(feats)
+        if not items:
+            raise ValueError("empty batch")
+        ts = []
+        for f in items:
+            t = f.detach() if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f))
+            if t.dim() != 2 or t.shape[1] < 1 or t.shape[0] != items[0].shape[0]:
+                raise ValueError("expected [K, T] features with one K and T >= 1, got %s" % (tuple(t.shape),))
+            ts.append(t.to(dev, torch.float32))
+        offs = np.zeros(len(ts) + 1, dtype=np.int64)
+        np.cumsum([t.shape[1] for t in ts], out=offs[1:])
+        b = torch.cat(ts, dim=1).contiguous() if len(ts) > 1 else ts[0].contiguous()
+    if rows is not None and b.shape[0] != rows:
+        raise ValueError("expected [%d, T] features, got %d rows" % (rows, b.shape[0]))
+    if not 1 <= b.shape[0] <= MAX_K:
+        raise ValueError("features have between 1 and %d rows, got %d" % (MAX_K, b.shape[0]))
+    if offs[-1] >= 2 ** 31:
+        raise ValueError("a bank holds at most 2^31 - 1 frames")
+    if not bool(torch.isfinite(b).all()):
+        raise ValueError("features must be finite")
+    return b, offs.astype(np.int32)
+
+
+def split(b, offs):
+    """(bank, offs) -> list of [K, T_i] views."""
+    return [b[:, int(offs[i]):int(offs[i + 1])] for i in range(len(offs) - 1)]
+
+
+def plan(x_offs, y_offs, want_path):
+    """HOST tables -> (table int64 [n, 6], workspace bytes, path rows) through ``mcvc_dtw_plan``; raises on what it refuses."""
+    L = _hip.lib()
+    x_offs = np.ascontiguousarray(x_offs, dtype=np.int32)
+    y_offs = np.ascontiguousarray(y_offs, dtype=np.int32)
+    n = x_offs.size - 1
+    if n < 1 or y_offs.size != x_offs.size:
+        raise ValueError("x and y must hold the same number (>= 1) of utterances, got %d and %d" % (x_offs.size - 1, y_offs.size - 1))
+    table = np.zeros((n, TABLE_COLS), dtype=np.int64)
+    ws, rows = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    rc = L.mcvc_dtw_plan(x_offs.ctypes.data, y_offs.ctypes.data, n, int(bool(want_path)), table.ctypes.data, ctypes.byref(ws), ctypes.byref(rows))
+    if rc != 0:
+        raise ValueError("mcvc_dtw_plan refused the batch (code %d): every utterance needs between 1 and %d frames" % (rc, L.mcvc_dtw_max_frames()))
+    return table, int(ws.value), int(rows.value)
+
+
+def dtw(x, y, scale=1.0, return_path=False):
+    """Ragged batch of pairs (utterance p of ``x`` against utterance p of ``y``) in one launch (two with paths), on the current stream.
+    -> (cost float32 [n], length int32 [n]) device tensors, and with ``return_path`` a list of int32 [length_p, 2] device tensors."""
+    xb, xo = bank(x)
+    yb, yo = bank(y, xb.device)
+    if xb.shape[0] != yb.shape[0]:
+        raise ValueError("x has %d feature rows, y has %d" % (xb.shape[0], yb.shape[0]))
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError("scale must be finite, got %r" % (scale,))
+    table, ws_bytes, rows = plan(xo, yo, return_path)
+    n = table.shape[0]
+    L = _hip.lib()
+    dev = xb.device
+    with torch.no_grad(), torch.cuda.device(dev):
+        table_d = torch.from_numpy(table).to(dev)
+        cost = torch.empty(n, dtype=torch.float32, device=dev)
+        length = torch.empty(n, dtype=torch.int32, device=dev)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        path = torch.empty(max(rows, 1), 2, dtype=torch.int32, device=dev) if return_path else None
+        _hip.check(L.mcvc_dtw_run(_hip.ptr(xb), xb.shape[1], _hip.ptr(yb), yb.shape[1], xb.shape[0], scale, xo.ctypes.data, yo.ctypes.data,
+                                  _hip.ptr(table_d), n, _hip.ptr(cost), _hip.ptr(length), _hip.ptr(path), _hip.ptr(ws), ws_bytes, _hip.stream()),
+                   "mcvc_dtw_run")
+        if not return_path:
+            return cost, length
+        lens = length.cpu().numpy()
+        paths = [path[int(table[p, 5]):int(table[p, 5]) + int(lens[p])] for p in range(n)]
+    return cost, length, paths
+
+
+def mel_cepstra(mels, n_cep=24):
+    """log10-mels (list of [80, T_i], or a bank) -> (cepstra bank float32 [n_cep, N] on the device, int32 offsets); one launch."""
+    b, offs = bank(mels, rows=N_MEL)
+    n_cep = int(n_cep)
+    if not 1 <= n_cep <= N_MEL - 1:
+        raise ValueError("n_cep must lie in 1 .. %d, got %r" % (N_MEL - 1, n_cep))
+    dev = b.device
+    key = (dev.index, n_cep)
+    basis = _basis.get(key)
+    if basis is None:
+        basis = _basis[key] = torch.from_numpy(host_basis(n_cep)).to(dev)
+    with torch.no_grad(), torch.cuda.device(dev):
+        out = torch.empty(n_cep, b.shape[1], dtype=torch.float32, device=dev)
+        _hip.check(_hip.lib().mcvc_cep_project(_hip.ptr(b), b.shape[1], _hip.ptr(basis), n_cep, _hip.ptr(out), _hip.stream()), "mcvc_cep_project")
+    return out, offs
+
+
+def mcd(converted_mels, target_mels, n_cep=24):
+    """Mel-cepstral distortion after DTW alignment, pair by pair -> dict: ``mcd`` (dB per pair, float64 numpy: float32 cost / length),
+    ``length`` (path lengths), ``frames_converted`` / ``frames_target``, ``mean``."""
+    cx, xo = mel_cepstra(converted_mels, n_cep)
+    cy, yo = mel_cepstra(target_mels, n_cep)
+    cost, length = dtw((cx, xo), (cy, yo), scale=MCD_SCALE)
+    cost, length = cost.cpu().numpy().astype(np.float64), length.cpu().numpy()
+    per = cost / length
+    return {"mcd": per, "length": length, "frames_converted": np.diff(xo), "frames_target": np.diff(yo), "mean": float(per.mean()), "n_cep": int(n_cep)}
