@@ -406,6 +406,36 @@ int mcvc_dtw_plan(const int* x_offs, const int* y_offs, int n_pairs, int want_pa
 int mcvc_dtw_run(const float* x, long long x_frames, const float* y, long long y_frames, int K, float scale, const int* x_offs, const int* y_offs,
                  const long long* table, int n_pairs, float* cost, int* length, int* path, void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- pitch tracking (new): YIN F0 contours on the front-end's frame grid and F0 statistics along DTW paths (csrc/f0_kernels.hip; the
+ *      definitions are in mask_cyclegan_vc/pitch.py and INTEGRATION.md).  22050 Hz, hop 256, integration window W = 1024.  Frame t of an
+ *      utterance (frames and work list: mcvc_audio_plan) is centred on sample c_t = 256 t + 128, the centre of mel frame t's window, and
+ *      reads buf[j] = x[c_t - (W + tau_max) / 2 + j], zero outside the utterance.  d(tau) = sum_{j < W} (buf[j] - buf[j + tau])^2, from
+ *      differences; d'(0) = 1, d'(tau) = d(tau) tau / sum_{1 <= k <= tau} d(k), 1 where that sum is 0.  Pick: the first tau in tau_min ..
+ *      tau_max with d'(tau) < threshold, then upward while d'(tau + 1) < d'(tau); with a, b, c = d'(tau - 1), d'(tau), d'(tau + 1):
+ *      off = 0 at tau_max or where den = (a - b) + (c - b) <= 0, else clamp(0.5 (a - c) / den, -0.5, 0.5); f0 = 22050 / (tau + off),
+ *      aperiodicity = b.  No lag under the threshold: f0 = 0 (unvoiced), aperiodicity = min d'.  Comparisons are strict, on the stored fp32 d'.
+ *        mcvc_f0_max_lag    the largest tau_max (640: 34.5 Hz).
+ *        mcvc_f0_launches   kernel launches of one mcvc_f0_track (1, with or without cmnd).
+ *        mcvc_f0_track      one launch on `stream`; no device allocation.  wave, tiles (mcvc_audio_plan's, uploaded, 16-byte aligned), f0 and
+ *                           aperiodicity fp32 [total_frames], cmnd (nullable) fp32 [tau_max + 1][total_frames] -- the d' the pick was made on --
+ *                           are DEVICE pointers.  A work item that does not lie inside [0, n_samples) x [0, total_frames) is skipped, never
+ *                           followed.  MCVC_ERR_INVALID, before any pointer is touched: a null or misaligned pointer, a lag range outside
+ *                           2 <= tau_min < tau_max <= 640, a threshold that is not finite or not in (0, 1], n_tiles < 1, total_frames < 1,
+ *                           n_samples < 385.
+ *        mcvc_f0_stats      one launch, one wavefront per pair.  fx [x_frames], fy [y_frames] fp32 F0 banks (0 = unvoiced); path int32 [rows][2]
+ *                           as mcvc_dtw_run wrote it (8-byte aligned); pairs int64 [n_pairs][4] (16-byte aligned): x frame offset, y frame
+ *                           offset, first path row, path rows -- DEVICE pointers all.  counts int32 [n_pairs][4]: rows with both sides voiced,
+ *                           x only, y only, neither; sums fp32 [n_pairs][2]: sum c and sum c^2 over the both-voiced rows, c = 1200 log2(fx / fy)
+ *                           cents.  Lane l takes rows l, l + 64, ... in order, then a fixed butterfly; no atomics: a batch equals its single
+ *                           calls bit for bit.  A path row that points outside the banks is skipped; the extent of `path` is the caller's
+ *                           contract.  MCVC_ERR_INVALID: a null or misaligned pointer, x_frames / y_frames / n_pairs < 1.               */
+int mcvc_f0_max_lag(void);
+int mcvc_f0_launches(int want_cmnd);
+int mcvc_f0_track(const float* wave, long long n_samples, const int* tiles, int n_tiles, int tau_min, int tau_max, float threshold, float* f0,
+                  float* aperiodicity, float* cmnd, long long total_frames, void* stream);
+int mcvc_f0_stats(const float* fx, long long x_frames, const float* fy, long long y_frames, const int* path, const long long* pairs, int n_pairs,
+                  int* counts, float* sums, void* stream);
+
 /* ---- single-op entry points (kernel parity tests; same kernels the network calls use) ---------- */
 /* y[N,Cout,OH,OW] = conv2d(x[N,Cin,H,W], w[Cout,Cin,KH,KW]) + bias ; stride 1 or 2.
  * wpack: scratch of mcvc_conv2d_pack_floats() floats, zero-initialised by the caller.

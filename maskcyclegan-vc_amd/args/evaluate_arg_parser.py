@@ -17,6 +17,14 @@ class EvaluateArgParser(object):
         ("--source_speaker_id", dict(type=str, default=None, help="Also report the unconverted baseline: the source speaker's preprocessed utterances "
                                      "against the same references.")),
         ("--n_cep", dict(type=int, default=24, help="Mel-cepstral coefficients c_1 .. c_n_cep (1 .. 79) from the 80-band log-mel.")),
+        ("--f0", dict(action="store_true", help="Also report F0 RMSE / bias in cents and the voiced/unvoiced error along the same DTW alignment: "
+                      "YIN on the GPU (mask_cyclegan_vc/pitch.py) over the converted .wav files and the target recordings.  Needs --target_wav_dir "
+                      "(preprocessed caches hold no audio).")),
+        ("--converted_audio_dir", dict(type=str, default=None, help="With --f0: folder of <i>-converted_<src>_to_<tgt>.wav files as mask_cyclegan_vc.test "
+                                       "writes them with a decoder.  Default: <save_dir>/<name>/converted_audio.")),
+        ("--f0_min", dict(type=float, default=60.0, help="With --f0: lowest F0 searched, Hz (longest lag floor(22050 / f0_min) <= 640).")),
+        ("--f0_max", dict(type=float, default=500.0, help="With --f0: highest F0 searched, Hz (shortest lag ceil(22050 / f0_max) >= 2).")),
+        ("--f0_threshold", dict(type=float, default=0.15, help="With --f0: YIN's threshold on the normalised difference function, in (0, 1].")),
     ]
 
     def __init__(self):
@@ -30,4 +38,12 @@ class EvaluateArgParser(object):
             self.parser.error("give the references as exactly one of --target_speaker_id and --target_wav_dir")
         if not 1 <= args.n_cep <= 79:
             self.parser.error("--n_cep takes a number of coefficients in 1 .. 79")
+        if args.f0 and args.target_wav_dir is None:
+            self.parser.error("--f0 needs the references as audio: give --target_wav_dir (preprocessed caches hold no waveforms)")
+        from mask_cyclegan_vc.pitch import check_threshold, lag_range
+        try:
+            lag_range(args.f0_min, args.f0_max)
+            check_threshold(args.f0_threshold)
+        except ValueError as exc:
+            self.parser.error(str(exc))
         return args

@@ -26,6 +26,7 @@
 #include "vocoder.h"
 #include "griffinlim.h"
 #include "dtw.h"
+#include "f0.h"
 #include "../../include/mcvc.h"
 #include <string.h>
 #include <algorithm>
@@ -2666,6 +2667,23 @@ int mcvc_dtw_run(const float* x, long long x_frames, const float* y, long long y
 {
     return mcvc_dtw_run_launch(x, x_frames, y, y_frames, K, scale, x_offs, y_offs, table, n_pairs, cost, length, path, workspace, workspace_bytes,
                                (hipStream_t)stream);
+}
+
+// ---- pitch tracking: YIN F0 contours and F0 statistics along DTW paths (f0_kernels.hip) ----
+int mcvc_f0_max_lag(void) { return MCVC_F0_MAX_LAG; }
+
+int mcvc_f0_launches(int want_cmnd) { (void)want_cmnd; return 1; }
+
+int mcvc_f0_track(const float* wave, long long n_samples, const int* tiles, int n_tiles, int tau_min, int tau_max, float threshold, float* f0,
+                  float* aperiodicity, float* cmnd, long long total_frames, void* stream)
+{
+    return mcvc_f0_track_launch(wave, n_samples, tiles, n_tiles, tau_min, tau_max, threshold, f0, aperiodicity, cmnd, total_frames, (hipStream_t)stream);
+}
+
+int mcvc_f0_stats(const float* fx, long long x_frames, const float* fy, long long y_frames, const int* path, const long long* pairs, int n_pairs,
+                  int* counts, float* sums, void* stream)
+{
+    return mcvc_f0_stats_launch(fx, x_frames, fy, y_frames, path, pairs, n_pairs, counts, sums, (hipStream_t)stream);
 }
 
 int mcvc_axpy(float* y, const float* x, float alpha, long long n, void* stream)

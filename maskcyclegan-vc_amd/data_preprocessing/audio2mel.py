@@ -121,6 +121,27 @@ def read_wav(path, sampling_rate=SAMPLING_RATE):
     return np.ascontiguousarray(x, dtype=np.float32)
 
 
+def plan_bank(lengths):
+    """Sample counts of a bank's utterances -> (sample offsets [n + 1], frame offsets [n + 1], the launch's work list [n_tiles, 4]) as int32
+    numpy, through ``mcvc_audio_plan``: the frame grid every kernel that works on waveform banks shares."""
+    from mask_cyclegan_vc._hip import check, lib
+    L = lib()
+    n = len(lengths)
+    offs = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.asarray(lengths, dtype=np.int64), out=offs[1:])
+    if n < 1 or offs[-1] >= 2 ** 31:
+        raise ValueError("a bank holds between 1 utterance and 2^31 - 1 samples")
+    for k in lengths:
+        num_frames(k)                                                  # raises for an utterance under 385 samples
+    offs = offs.astype(np.int32)
+    frame_offs = np.zeros(n + 1, dtype=np.int32)
+    n_tiles = ctypes.c_int(0)
+    check(L.mcvc_audio_plan(offs.ctypes.data, n, frame_offs.ctypes.data, None, 0, ctypes.byref(n_tiles)), "mcvc_audio_plan")
+    tiles = np.zeros((n_tiles.value, 4), dtype=np.int32)
+    check(L.mcvc_audio_plan(offs.ctypes.data, n, frame_offs.ctypes.data, tiles.ctypes.data, n_tiles.value, ctypes.byref(n_tiles)), "mcvc_audio_plan")
+    return offs, frame_offs, tiles
+
+
 class Audio2Mel(object):
     """The vocoder's front-end as a callable: ``fft(x)`` with ``x`` a HIP-device tensor [B, 1, L] or [B, L] -> [B, 80, T]
     (the convention of the reference's ``vocoder.fft``), and ``fft.bank(waveforms)`` for utterances of different lengths:
@@ -153,25 +174,12 @@ class Audio2Mel(object):
         """wave: contiguous float32 device tensor holding the utterances back to back -> ([80, total_frames] device tensor, frame offsets)."""
         import torch
         from mask_cyclegan_vc._hip import check, lib, ptr, stream
-        L = lib()
-        n = len(lengths)
-        offs = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(np.asarray(lengths, dtype=np.int64), out=offs[1:])
-        if n < 1 or offs[-1] >= 2 ** 31:
-            raise ValueError("a bank holds between 1 utterance and 2^31 - 1 samples")
-        for k in lengths:
-            num_frames(k)                                              # raises for an utterance under 385 samples
-        offs = offs.astype(np.int32)
-        frame_offs = np.zeros(n + 1, dtype=np.int32)
-        n_tiles = ctypes.c_int(0)
-        check(L.mcvc_audio_plan(offs.ctypes.data, n, frame_offs.ctypes.data, None, 0, ctypes.byref(n_tiles)), "mcvc_audio_plan")
-        tiles = np.zeros((n_tiles.value, 4), dtype=np.int32)
-        check(L.mcvc_audio_plan(offs.ctypes.data, n, frame_offs.ctypes.data, tiles.ctypes.data, n_tiles.value, ctypes.byref(n_tiles)), "mcvc_audio_plan")
+        offs, frame_offs, tiles = plan_bank(lengths)
         total = int(frame_offs[-1])
         with torch.cuda.device(self.device):
             tiles_d = torch.from_numpy(tiles).to(self.device)
             out = torch.empty(N_MEL, total, dtype=torch.float32, device=self.device)
-            check(L.mcvc_audio_log_mel(ptr(wave), int(offs[-1]), ptr(tiles_d), n_tiles.value, ptr(self.basis()), ptr(out), total, stream()),
+            check(lib().mcvc_audio_log_mel(ptr(wave), int(offs[-1]), ptr(tiles_d), tiles.shape[0], ptr(self.basis()), ptr(out), total, stream()),
                   "mcvc_audio_log_mel")
         return out, frame_offs
 

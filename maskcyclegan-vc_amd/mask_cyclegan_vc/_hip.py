@@ -121,6 +121,10 @@ _SIGS = {
     "mcvc_dtw_plan": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.POINTER(c_longlong), ctypes.POINTER(c_longlong)]),
     "mcvc_dtw_run": (c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_longlong, c_void_p]),
+    "mcvc_f0_max_lag": (c_int, []),
+    "mcvc_f0_launches": (c_int, [c_int]),
+    "mcvc_f0_track": (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "mcvc_f0_stats": (c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "mcvc_axpy": (c_int, [c_void_p, c_void_p, c_float, c_longlong, c_void_p]),
     "mcvc_conv2d_pack_floats": (c_longlong, [c_int, c_int, c_int, c_int]),
     "mcvc_conv2d_forward": (c_int, [c_void_p] * 6 + [c_int] * 12 + [c_void_p]),

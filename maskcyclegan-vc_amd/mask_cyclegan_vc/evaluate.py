@@ -14,7 +14,12 @@ baseline (source against target), the usual second column.
 
 Output: ``<save_dir>/<name>/metrics.json`` (per utterance: MCD, path length, frames of both sides; mean, std, median; n_cep; the baseline
 if asked) and one printed summary line.  The cepstra come from the 80-band mel spectrum, not from WORLD: the numbers compare runs of this
-project, not tables in papers."""
+project, not tables in papers.
+
+``--f0`` (needs ``--target_wav_dir``) adds the pitch columns: F0 RMSE and bias in cents and the voiced/unvoiced error along the same DTW
+alignment (mask_cyclegan_vc/pitch.py, metrics.f0_distortion), from the ``<i>-converted_*.wav`` files of ``--converted_audio_dir`` (default
+``<save_dir>/<name>/converted_audio``, what ``mask_cyclegan_vc.test`` writes with a decoder) and the target recordings.  Without the flag the
+run and its ``metrics.json`` are what they were."""
 import glob
 import json
 import os
@@ -28,6 +33,9 @@ from . import metrics
 from .utils import denormalize_mel
 
 _NAME = re.compile(r"^(\d+)-converted_.*\.npy$")
+_WAV_NAME = re.compile(r"^(\d+)-converted_.*\.wav$")
+F0_UNIT = ("cents = 1200 log2(f0 converted / f0 target) over the DTW path rows where both sides are voiced; vuv_error = path rows where exactly one "
+           "side is voiced / path length; YIN on decoded audio (not WORLD / Harvest)")
 
 
 def converted_files(folder):
@@ -53,12 +61,34 @@ def speaker_mels(preprocessed_dir, speaker_id):
     return [denormalize_mel(np.asarray(m, dtype=np.float32), mean, std).astype(np.float32) for m in mels]
 
 
-def wav_dir_mels(folder):
-    from data_preprocessing.audio2mel import Audio2Mel, read_wav
+def wav_dir_waves(folder):
+    from data_preprocessing.audio2mel import read_wav
     files = sorted(glob.glob(os.path.join(folder, "**", "*.wav"), recursive=True))
     if not files:
         raise ValueError("no .wav files under %s" % folder)
-    return Audio2Mel().bank([read_wav(f) for f in files])
+    return [read_wav(f) for f in files]
+
+
+def converted_waves(folder, ids):
+    """The <i>-converted_*.wav of every index in ``ids`` -> list of float32 waveforms."""
+    from data_preprocessing.audio2mel import read_wav
+    found = {}
+    for p in sorted(glob.glob(os.path.join(folder, "*.wav"))):
+        m = _WAV_NAME.match(os.path.basename(p))
+        if m:
+            if int(m.group(1)) in found:
+                raise ValueError("%s holds several .wav files for one utterance index (two conversions in one folder?)" % folder)
+            found[int(m.group(1))] = p
+    for i in ids:
+        if i not in found:
+            raise ValueError("converted utterance %d has no converted audio: no %d-converted_*.wav under %s (mask_cyclegan_vc.test writes them "
+                             "with --vocoder_ckpt or --griffin_lim)" % (i, i, folder))
+    return [read_wav(found[i]) for i in ids]
+
+
+def _voiced_median(tracks):
+    v = np.concatenate([t[t > 0] for t in tracks]) if tracks else np.zeros(0)
+    return float(np.median(v)) if v.size else None
 
 
 def _pick(refs, ids, what):
@@ -80,7 +110,9 @@ def evaluate(args):
     ids = [i for i, _ in files]
     converted = [np.load(p).astype(np.float32) for _, p in files]
     if args.target_wav_dir:
-        refs = wav_dir_mels(args.target_wav_dir)
+        from data_preprocessing.audio2mel import Audio2Mel
+        ref_waves = wav_dir_waves(args.target_wav_dir)
+        refs = Audio2Mel().bank(ref_waves)
     else:
         refs = speaker_mels(args.preprocessed_data_dir, args.target_speaker_id)
     target = _pick(refs, ids, "reference")
@@ -100,6 +132,22 @@ def evaluate(args):
     report.update(_stats(res["mcd"]))
     if base is not None:
         report["baseline"] = _stats(base["mcd"])
+    if args.f0:
+        from .pitch import PitchTracker
+        tracker = PitchTracker(fmin=args.f0_min, fmax=args.f0_max, threshold=args.f0_threshold)
+        f0 = metrics.f0_distortion(converted_waves(args.converted_audio_dir or os.path.join(run_dir, "converted_audio"), ids),
+                                   _pick(ref_waves, ids, "reference"), converted, target, args.n_cep, tracker)
+        for k, u in enumerate(utts):
+            some = int(f0["voiced_pairs"][k]) > 0                       # (a pair without a both-voiced row has no cent figures: null)
+            u.update(f0_rmse_cents=float(f0["rmse_cents"][k]) if some else None, f0_bias_cents=float(f0["bias_cents"][k]) if some else None,
+                     vuv_error=float(f0["vuv_error"][k]), voiced_pairs=int(f0["voiced_pairs"][k]))
+        keep = f0["voiced_pairs"] > 0
+        report["f0"] = {"n_utterances_voiced": int(keep.sum()), "tau_min": int(tracker.lags[0]), "tau_max": int(tracker.lags[1]),
+                        "f0_min": float(args.f0_min), "f0_max": float(args.f0_max), "threshold": float(tracker.threshold),
+                        "median_f0_converted_hz": _voiced_median(f0["f0_converted"]), "median_f0_target_hz": _voiced_median(f0["f0_target"]),
+                        "unit": F0_UNIT}
+        for key in ("rmse_cents", "bias_cents", "vuv_error"):
+            report["f0"][key] = _stats(f0[key][keep]) if keep.any() else None
     os.makedirs(run_dir, exist_ok=True)
     out = os.path.join(run_dir, "metrics.json")
     with open(out, "w") as fh:
@@ -107,6 +155,11 @@ def evaluate(args):
     line = "MCD over %d utterances (n_cep %d): mean %.3f dB, std %.3f, median %.3f" % (len(utts), args.n_cep, report["mean"], report["std"], report["median"])
     if base is not None:
         line += " | unconverted baseline: mean %.3f dB" % report["baseline"]["mean"]
+    if args.f0 and report["f0"]["rmse_cents"] is not None:
+        line += " | F0 RMSE %.1f cents, bias %+.1f cents, V/UV error %.1f %% (%d utterances with voiced pairs)" % (
+            report["f0"]["rmse_cents"]["mean"], report["f0"]["bias_cents"]["mean"], 100.0 * report["f0"]["vuv_error"]["mean"], report["f0"]["n_utterances_voiced"])
+    elif args.f0:
+        line += " | F0: no utterance with a voiced pair"
     print(line + " -> " + out)
     return report
 

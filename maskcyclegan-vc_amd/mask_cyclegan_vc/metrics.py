@@ -3,7 +3,9 @@
 
 * ``dtw(x, y, scale=1.0, return_path=False)``   ragged batch of pairs -> cost [n], length [n] (and the warping paths);
 * ``mel_cepstra(mels, n_cep=24)``               log10-mels [80, T_i] -> cepstra bank ([n_cep, N], offsets);
-* ``mcd(converted_mels, target_mels, n_cep=24)`` -> per-pair dB, path lengths and the mean.
+* ``mcd(converted_mels, target_mels, n_cep=24)`` -> per-pair dB, path lengths and the mean;
+* ``f0_stats(f0_x, f0_y, paths)``                F0 tracks + warping paths -> per-pair F0 RMSE / bias in cents and voiced/unvoiced error;
+* ``f0_distortion(conv_wavs, tgt_wavs, conv_mels, tgt_mels, n_cep=24, tracker=None)`` -> the same from waveforms and their log-mels.
 
 Definitions (tests/dtw_checker.py restates them in float64):
 
@@ -26,6 +28,12 @@ project with one another (checkpoints, ``--dtype`` settings, decoders), not with
 
 A batch equals its single calls bit for bit: every pair is one wavefront that sees only its own two utterances.  The default call writes
 no Tx x Ty matrix; ``return_path=True`` stores one direction byte per cell and a second launch walks them back.
+
+F0 statistics (csrc/f0_kernels.hip through ``mcvc_f0_stats``; the tracks come from mask_cyclegan_vc/pitch.py, 0 = unvoiced).  Over the rows
+(i, j) of a pair's warping path: counts of rows with both sides voiced, x only, y only, neither; over the both-voiced rows
+c = 1200 log2(fx[i] / fy[j]) cents, ``bias_cents`` = mean c, ``rmse_cents`` = sqrt(mean c^2), ``vuv_error`` = (x only + y only) / length.
+A pair without a both-voiced row has ``voiced_pairs`` 0 and ``nan`` for the two cent figures: a documented value, not an exception.
+One wavefront per pair, a fixed reduction order, no atomics: a batch equals its single calls bit for bit.
 """
 import ctypes
 import math
@@ -193,3 +201,86 @@ def mcd(converted_mels, target_mels, n_cep=24):
     cost, length = cost.cpu().numpy().astype(np.float64), length.cpu().numpy()
     per = cost / length
     return {"mcd": per, "length": length, "frames_converted": np.diff(xo), "frames_target": np.diff(yo), "mean": float(per.mean()), "n_cep": int(n_cep)}
+
+
+def _tracks(tracks, dev):
+    """list of 1-D F0 tracks -> (float32 device bank [N], int64 offsets [n + 1])."""
+    ts = []
+    for f in tracks:
+        t = f.detach() if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f))
+        if t.dim() != 1 or t.numel() < 1:
+            raise ValueError("expected 1-D F0 tracks of at least one frame, got %s" % (tuple(t.shape),))
+        ts.append(t.to(dev, torch.float32))
+    offs = np.zeros(len(ts) + 1, dtype=np.int64)
+    np.cumsum([t.numel() for t in ts], out=offs[1:])
+    return (torch.cat(ts) if len(ts) > 1 else ts[0]).contiguous(), offs
+
+
+def f0_stats(f0_x, f0_y, paths):
+    """F0 tracks (lists of [T_i], 0 = unvoiced) and the pairs' warping paths (list of int32 [length_p, 2], as ``dtw(..., return_path=True)``
+    returns them) -> dict of numpy arrays over the pairs: ``rmse_cents``, ``bias_cents`` (float64; nan where ``voiced_pairs`` is 0),
+    ``vuv_error``, ``voiced_pairs``, ``length``, and the raw ``counts`` [n, 4] (both voiced, x only, y only, neither).  One launch."""
+    dev = _device()
+    f0_x, f0_y, paths = list(f0_x), list(f0_y), list(paths)
+    n = len(paths)
+    if n < 1 or len(f0_x) != n or len(f0_y) != n:
+        raise ValueError("f0_x, f0_y and paths must hold the same number (>= 1) of utterances, got %d, %d and %d" % (len(f0_x), len(f0_y), n))
+    fx, xo = _tracks(f0_x, dev)
+    fy, yo = _tracks(f0_y, dev)
+    ps = []
+    for k, p in enumerate(paths):
+        t = p.detach() if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p))
+        if t.dim() != 2 or t.shape[1] != 2 or t.shape[0] < 1 or t.dtype not in (torch.int32, torch.int64):
+            raise ValueError("path %d: expected integer [length, 2] rows, got %s %s" % (k, t.dtype, tuple(t.shape)))
+        t = t.to(dev, torch.int32)
+        lo, hi = t.amin(dim=0).cpu().numpy(), t.amax(dim=0).cpu().numpy()
+        if lo.min() < 0 or hi[0] >= xo[k + 1] - xo[k] or hi[1] >= yo[k + 1] - yo[k]:
+            raise ValueError("path %d leaves its utterances of %d and %d frames" % (k, xo[k + 1] - xo[k], yo[k + 1] - yo[k]))
+        ps.append(t)
+    po = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum([t.shape[0] for t in ps], out=po[1:])
+    table = np.stack([xo[:-1], yo[:-1], po[:-1], np.diff(po)], axis=1).astype(np.int64)
+    with torch.no_grad(), torch.cuda.device(dev):
+        path = (torch.cat(ps, dim=0) if n > 1 else ps[0]).contiguous()
+        table_d = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
+        counts = torch.empty(n, 4, dtype=torch.int32, device=dev)
+        sums = torch.empty(n, 2, dtype=torch.float32, device=dev)
+        _hip.check(_hip.lib().mcvc_f0_stats(_hip.ptr(fx), fx.numel(), _hip.ptr(fy), fy.numel(), _hip.ptr(path), _hip.ptr(table_d), n,
+                                            _hip.ptr(counts), _hip.ptr(sums), _hip.stream()), "mcvc_f0_stats")
+        counts, sums = counts.cpu().numpy(), sums.cpu().numpy().astype(np.float64)
+    length = np.diff(po)
+    voiced = counts[:, 0].astype(np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        bias = np.where(voiced > 0, sums[:, 0] / voiced, np.nan)
+        rmse = np.where(voiced > 0, np.sqrt(sums[:, 1] / voiced), np.nan)
+    return {"rmse_cents": rmse, "bias_cents": bias, "vuv_error": (counts[:, 1] + counts[:, 2]).astype(np.float64) / length, "voiced_pairs": voiced,
+            "length": length, "counts": counts}
+
+
+def f0_distortion(conv_wavs, tgt_wavs, conv_mels, tgt_mels, n_cep=24, tracker=None):
+    """F0 RMSE / bias (cents) and voiced/unvoiced error of converted against target utterances, aligned by the DTW over their mel cepstra
+    (the alignment ``mcd`` scores): cepstra, DTW with paths, the F0 banks of both sides, the statistics -> the dict of ``f0_stats`` plus the
+    tracks ``f0_converted`` / ``f0_target`` (lists of float32 numpy), ``lags`` and ``threshold``.  A waveform whose frame count differs
+    from its mel's is a ValueError that names the utterance."""
+    from .pitch import PitchTracker
+    from data_preprocessing.audio2mel import num_frames
+    conv_wavs, tgt_wavs, conv_mels, tgt_mels = list(conv_wavs), list(tgt_wavs), list(conv_mels), list(tgt_mels)
+    n = len(conv_mels)
+    if n < 1 or len(conv_wavs) != n or len(tgt_wavs) != n or len(tgt_mels) != n:
+        raise ValueError("waveforms and mels of both sides must hold the same number (>= 1) of utterances, got %d, %d, %d and %d"
+                         % (len(conv_wavs), len(tgt_wavs), n, len(tgt_mels)))
+    for side, wavs, mels in (("converted", conv_wavs, conv_mels), ("target", tgt_wavs, tgt_mels)):
+        for k, (w, m) in enumerate(zip(wavs, mels)):
+            samples = int(np.prod(w.shape))
+            if num_frames(samples) != m.shape[-1]:
+                raise ValueError("utterance %d (%s): a waveform of %d samples has %d frames, its mel has %d"
+                                 % (k, side, samples, num_frames(samples), m.shape[-1]))
+    cx, xo = mel_cepstra(conv_mels, n_cep)
+    cy, yo = mel_cepstra(tgt_mels, n_cep)
+    _, _, paths = dtw((cx, xo), (cy, yo), scale=MCD_SCALE, return_path=True)
+    tracker = PitchTracker(cx.device) if tracker is None else tracker
+    fx = [f for f, _ in tracker.bank(conv_wavs)]
+    fy = [f for f, _ in tracker.bank(tgt_wavs)]
+    res = f0_stats(fx, fy, paths)
+    res.update(f0_converted=fx, f0_target=fy, lags=tracker.lags, threshold=tracker.threshold)
+    return res
