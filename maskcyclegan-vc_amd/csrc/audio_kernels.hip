@@ -7,22 +7,22 @@
 // The transform is a matrix product.  The frame matrix of an utterance is its padded audio read with a row stride of 256 samples; a
 // workgroup stages the samples of 64 consecutive frames of ONE utterance in LDS once (63 * 256 + 1024 floats; the reflection at the
 // utterance's own two ends is index arithmetic at that point, so a neighbour in the bank is never read) and multiplies them with the
-// windowed cos / sin basis on v_mfma_f32_32x32x2_f32:  M = basis column (1024), N = frame (64), K = sample in frame (1024).
+// windowed cos / sin basis on v_mfma_f32_32x32x2_f32:  M = basis column (1024), N = frame (64), K = sample in frame (1024).  The tile's
+// constants, the reflected loader, the product and the accumulator mapping are the STFT tile engine's (stft.h), which the Griffin-Lim
+// decoder shares; this file adds the basis' element formula and the magnitude / mel / log epilogue.
 //
 // Basis layout (mcvc_audio_basis_init).  Column 2b is hann * cos and column 2b + 1 hann * sin of bin b = 0..511, so accumulator rows
 // (2b, 2b + 1) of a lane are the real and imaginary part of one (bin, frame): the magnitude needs no cross-lane traffic.  The sine column
 // of bin 0 is identically zero; it carries the cosine column of bin 512 (Nyquist, hann * (-1)^k, whose sine is zero as well) instead, so
 // 513 bins fit 1024 columns = 32 MFMA row tiles, four per wave.  The eight waves split M, so every basis element is used by exactly one
-// wave of a workgroup: it goes from L2 straight to registers (no LDS), pre-arranged on the host in the order the lanes consume it --
-// float index ((mt * 128 + kg) * 64 + lane) * 4 + j  =  W[k = 8 kg + 2 j + (lane >> 5)][column 32 mt + (lane & 31)] -- one coalesced
-// 16-byte load per lane, row tile and eight k.
+// wave of a workgroup: it goes from L2 straight to registers (no LDS), in the lane order of stft.h.
 //
 // The spectrum never leaves the chip: magnitudes go to LDS ([513][64], over the dead sample stage), the 513 -> 80 mel product runs from
 // there (each bin feeds at most two filters: per filter a contiguous bin range and its weights, summed in ascending bin order by one
 // thread per (filter, frame) -- no atomics, so a frame's value does not depend on what else is in the launch), then log10 / clamp and a
 // store of 64 consecutive floats per mel row.
 #include "mcvc_common.h"
-#include "audio.h"
+#include "stft.h"
 #include "trace.h"
 
 #include <cmath>
@@ -31,15 +31,11 @@
 
 namespace {
 
-constexpr int HOP = MCVC_AUDIO_HOP, NFFT = MCVC_AUDIO_NFFT, PAD = (NFFT - HOP) / 2, NBIN = NFFT / 2 + 1, NMEL = MCVC_AUDIO_NMEL;
-constexpr int TF = MCVC_AUDIO_TILE_FRAMES;                 // frames per workgroup
-constexpr int SPAN = (TF - 1) * HOP + NFFT;                // samples the frames of a tile cover
-constexpr int SPAN_LDS = SPAN + SPAN / 256 + 1;            // stored with one float of skew per 256: frame n starts at 257 n (conflict-free B reads)
+using namespace stft;
+
 constexpr int MAG_FLOATS = NBIN * TF;
 constexpr int LDS_FLOATS = MAG_FLOATS > SPAN_LDS ? MAG_FLOATS : SPAN_LDS;
-constexpr int KG = NFFT / 8;                               // k groups of 8 (one 16-byte basis load per lane and row tile)
-constexpr int NTHREADS = 512, MT_PER_WAVE = 4;         // eight waves split the 32 row tiles: 128 accumulator registers each, two waves per SIMD
-constexpr long long DFT_FLOATS = (long long)NFFT * NFFT;   // 1024 columns x 1024 k
+constexpr int MT_PER_WAVE = 4;                             // eight waves split the 32 row tiles: 128 accumulator registers each, two waves per SIMD
 constexpr int TAB_HEAD = 256;                              // int32 lo[80] | count[80] | weight offset[80] | pad
 
 struct AudioArgs {
@@ -56,77 +52,23 @@ __global__ void __launch_bounds__(NTHREADS) audio_log_mel_kernel(const AudioArgs
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, half = lane >> 5;
-    const int4 tile = reinterpret_cast<const int4*>(a.tiles)[blockIdx.x];
-    const long long s0 = tile.x;
-    const int L = tile.y, t0 = tile.w;
-    const long long col0 = tile.z;
-    // what the plan (mcvc_audio_plan) guarantees, checked again: a table that does not describe this bank reads and writes nothing
-    if (L < PAD + 1 || s0 < 0 || s0 + L > a.n_samples || t0 < 0 || col0 < 0) return;
-    const int T = (L - HOP) / HOP + 1;
-    long long nv_ll = (long long)T - t0;
-    if (nv_ll > TF) nv_ll = TF;
-    if (nv_ll > a.total_frames - col0) nv_ll = a.total_frames - col0;
-    const int nv = (int)nv_ll;
+    const BankTile tile(a.tiles, a.n_samples, a.total_frames);
+    const long long col0 = tile.col0;
+    const int nv = tile.nv;
     if (nv < 1) return;
 
-    // ---- the tile's samples, reflected at the utterance's own ends (F.pad 'reflect': the edge sample is not repeated) ----
-    const float* const src = a.wave + s0;
-    const int p0 = t0 * HOP - PAD;                          // index in the utterance of the tile's first padded sample
-    const int s_end = (nv - 1) * HOP + NFFT;                // samples the valid frames cover
-    for (int s = tid; s < SPAN; s += NTHREADS) {
-        float v = 0.f;
-        if (s < s_end) {
-            int i = p0 + s;
-            if (i < 0) i = -i;
-            if (i >= L) i = 2 * (L - 1) - i;
-            if (i >= 0 && i < L) v = src[i];                // (always true for a valid frame: L >= 385 > 384)
-        }
-        smem[s + (s >> 8)] = v;
-    }
-    __syncthreads();
+    // ---- the tile's samples, reflected at the utterance's own ends ----
+    const float* const src = a.wave + tile.s0;
+    stft_stage_tile(smem, tile.t0, nv, tile.L, [&](int i) { return src[i]; });
 
-    // ---- spectrum: acc[mt][nt] = rows 32 (8 wave + mt) .. + 31 of the basis x frames 32 nt .. + 31 ----
+    // ---- spectrum: acc[mt][nt] = rows 32 (4 wave + mt) .. + 31 of the basis x frames 32 nt .. + 31 ----
     f32x16 acc[MT_PER_WAVE][2];
-#pragma unroll
-    for (int mt = 0; mt < MT_PER_WAVE; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
+    stft_zero(acc);
     const f32x4* const ap = reinterpret_cast<const f32x4*>(a.basis) + (long long)wave * MT_PER_WAVE * KG * 64 + lane;
-    const float* const b_lane0 = smem + 257 * l31 + half;
-    const float* const b_lane1 = b_lane0 + 257 * 32;
-    // two register stages of the basis, filled one k group ahead: a wave's loads of group kg + 1 fly under its MFMAs of group kg
-    f32x4 st0[MT_PER_WAVE], st1[MT_PER_WAVE];
-    auto fetch = [&](f32x4 (&st)[MT_PER_WAVE], int kg) {
-#pragma unroll
-        for (int mt = 0; mt < MT_PER_WAVE; ++mt) st[mt] = ap[((long long)mt * KG + kg) * 64];
-    };
-    auto multiply = [&](const f32x4 (&st)[MT_PER_WAVE], int kg) {
-        const int kb = 8 * kg + (kg >> 5);                  // k = 8 kg + 2 j + half sits at 257 n + k + (k >> 8)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float b0 = b_lane0[kb + 2 * j], b1 = b_lane1[kb + 2 * j];
-#pragma unroll
-            for (int mt = 0; mt < MT_PER_WAVE; ++mt) {
-                acc[mt][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(st[mt][j], b0, acc[mt][0], 0, 0, 0);
-                acc[mt][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(st[mt][j], b1, acc[mt][1], 0, 0, 0);
-            }
-        }
-    };
-    fetch(st0, 0);
-#pragma unroll 1
-    for (int kg = 0; kg < KG; kg += 2) {
-        fetch(st1, kg + 1);
-        __builtin_amdgcn_sched_barrier(0);                  // (left alone, the scheduler sinks the loads to half a group before their use)
-        multiply(st0, kg);
-        fetch(st0, kg + 2 < KG ? kg + 2 : kg);              // (the last one is a repeat nobody uses)
-        __builtin_amdgcn_sched_barrier(0);
-        multiply(st1, kg + 1);
-    }
+    stft_product<MT_PER_WAVE, 0, true>(acc, ap, stft_b_lane(smem, l31, half), 0, KG);
     __syncthreads();                                        // every wave is done with the samples: the magnitudes take their place
 
-    // ---- magnitude: accumulator row 8 q + 4 half + i of a tile is basis column 32 mt + that; rows (2 pr, 2 pr + 1) = (re, im) of one bin ----
+    // ---- magnitude: rows (2 bin, 2 bin + 1) = (re, im) of one bin ----
 #pragma unroll
     for (int mt = 0; mt < MT_PER_WAVE; ++mt) {
         __builtin_amdgcn_sched_barrier(0);                  // (one row tile at a time)
@@ -137,8 +79,8 @@ __global__ void __launch_bounds__(NTHREADS) audio_log_mel_kernel(const AudioArgs
 #pragma unroll
                 for (int pr = 0; pr < 2; ++pr) {
                     const float re = acc[mt][nt][4 * q + 2 * pr], im = acc[mt][nt][4 * q + 2 * pr + 1];
-                    const int bin = 16 * (wave * MT_PER_WAVE + mt) + 4 * q + 2 * half + pr;
-                    const int n = l31 + 32 * nt;
+                    const int bin = stft_pair(wave * MT_PER_WAVE + mt, q, half) + pr;
+                    const int n = stft_col(l31, nt);
                     if (bin == 0) {                         // (real DC, real Nyquist) share the pair
                         smem[n] = fabsf(re);
                         smem[(NBIN - 1) * TF + n] = fabsf(im);
@@ -161,9 +103,7 @@ __global__ void __launch_bounds__(NTHREADS) audio_log_mel_kernel(const AudioArgs
     }
 }
 
-// ---- host: the Slaney mel filterbank and the windowed DFT basis, in float64 ----
-const double kPi = 3.14159265358979323846;
-
+// ---- host: the Slaney mel filterbank, in float64 ----
 double hz_to_mel(double f)
 {
     const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = std::log(6.4) / 27.0;
@@ -219,22 +159,12 @@ long long mcvc_audio_basis_floats_of() { return DFT_FLOATS + TAB_HEAD + (long lo
 
 void mcvc_audio_basis_fill(float* out)
 {
-    std::vector<double> hann(NFFT), cs(NFFT), sn(NFFT);
-    for (int k = 0; k < NFFT; ++k) {
-        hann[k] = 0.5 - 0.5 * std::cos(2.0 * kPi * k / NFFT);             // periodic (torch.hann_window)
-        cs[k] = std::cos(2.0 * kPi * k / NFFT);
-        sn[k] = std::sin(2.0 * kPi * k / NFFT);
-    }
-    for (int mt = 0; mt < NFFT / 32; ++mt)
-        for (int kg = 0; kg < KG; ++kg)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 4; ++j) {
-                    const int k = 8 * kg + 2 * j + (lane >> 5), m = 32 * mt + (lane & 31);
-                    const int bin = m == 1 ? NFFT / 2 : m >> 1;            // column 1: the Nyquist cosine
-                    const int ph = (int)(((long long)k * bin) % NFFT);     // exact argument reduction
-                    const double v = (m == 1 || !(m & 1)) ? cs[ph] : sn[ph];
-                    out[(((long long)mt * KG + kg) * 64 + lane) * 4 + j] = (float)(hann[k] * v);
-                }
+    const Tables w;
+    stft_fill_lane_order(out, [&](int k, int m) {           // row m of the basis, sample k
+        const int bin = m == 1 ? NFFT / 2 : m >> 1;         // row 1: the Nyquist cosine
+        const int ph = stft_phase(k, bin);
+        return w.hann[k] * ((m == 1 || !(m & 1)) ? w.cs[ph] : w.sn[ph]);
+    });
     const MelTable& t = mel_table();
     int* head = reinterpret_cast<int*>(out + DFT_FLOATS);
     for (int i = 0; i < TAB_HEAD; ++i) head[i] = 0;

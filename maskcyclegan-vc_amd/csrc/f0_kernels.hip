@@ -29,7 +29,6 @@
 namespace {
 
 constexpr int W = MCVC_F0_WINDOW, HOP = MCVC_AUDIO_HOP, MAXLAG = MCVC_F0_MAX_LAG, FS = MCVC_F0_SUB_FRAMES, TF = MCVC_AUDIO_TILE_FRAMES;
-constexpr int PAD = (MCVC_AUDIO_NFFT - HOP) / 2;               // the front-end's rule: an utterance has more than 384 samples
 constexpr int NBLK = FS + W / HOP - 1;                         // 11 blocks of one hop cover eight windows
 constexpr int MAXTHREADS = 192;                                // 4 lags per lane: 768 >= MAXLAG + 1
 constexpr int XS = NBLK * HOP + 4 * MAXTHREADS + 8;            // staged samples: the last lane's window read stays inside
@@ -53,18 +52,12 @@ __global__ __launch_bounds__(MAXTHREADS) void f0_track_kernel(const F0Args a)
     __shared__ __attribute__((aligned(16))) float smem[SMEM];
     const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = nthr >> 6;
-    const int4 tile = reinterpret_cast<const int4*>(a.tiles)[blockIdx.x];
-    const long long s0 = tile.x, col0 = tile.z;
-    const int L = tile.y, t0 = tile.w;
-    // what the plan (mcvc_audio_plan) guarantees, checked again: a table that does not describe this bank reads and writes nothing
-    if (L < PAD + 1 || s0 < 0 || s0 + L > a.n_samples || t0 < 0 || col0 < 0) return;
-    const int T = (L - HOP) / HOP + 1;
-    long long nv = (long long)T - t0;
-    if (nv > TF) nv = TF;
-    if (nv > a.total_frames - col0) nv = a.total_frames - col0;
+    const BankTile tile(a.tiles, a.n_samples, a.total_frames);
+    const long long s0 = tile.s0, col0 = tile.col0;
+    const int L = tile.L, t0 = tile.t0;
     const int fb = FS * blockIdx.y;                             // the sub-tile's first frame inside the tile
-    if (nv - fb < 1) return;                                    // (uniform: the whole workgroup leaves before its first barrier)
-    const int nvf = nv - fb < FS ? (int)(nv - fb) : FS;
+    if (tile.nv - fb < 1) return;                               // (uniform: the whole workgroup leaves before its first barrier)
+    const int nvf = tile.nv - fb < FS ? tile.nv - fb : FS;
     const int tau_min = a.tau_min, tau_max = a.tau_max;
 
     // ---- the sub-tile's samples; outside [0, L) of this utterance they are zero, never the neighbour's ----
@@ -232,7 +225,7 @@ __global__ __launch_bounds__(64) void f0_stats_kernel(const F0StatArgs a)
 int mcvc_f0_track_launch(const float* wave, long long n_samples, const int* tiles, int n_tiles, int tau_min, int tau_max, float threshold,
                          float* f0, float* aperiodicity, float* cmnd, long long total_frames, hipStream_t s)
 {
-    if (!wave || !tiles || !f0 || !aperiodicity || n_samples < PAD + 1 || n_tiles < 1 || total_frames < 1 || total_frames > 0x7fffffffLL) return MCVC_ERR_INVALID;
+    if (!wave || !tiles || !f0 || !aperiodicity || n_samples < MCVC_AUDIO_PAD + 1 || n_tiles < 1 || total_frames < 1 || total_frames > 0x7fffffffLL) return MCVC_ERR_INVALID;
     if (((uintptr_t)wave & 3) || ((uintptr_t)f0 & 3) || ((uintptr_t)aperiodicity & 3) || ((uintptr_t)cmnd & 3) || ((uintptr_t)tiles & 15)) return MCVC_ERR_INVALID;
     if (!(tau_min >= 2 && tau_min < tau_max && tau_max <= MAXLAG)) return MCVC_ERR_INVALID;
     if (!(threshold > 0.f && threshold <= 1.f)) return MCVC_ERR_INVALID;              // (a NaN fails both comparisons)

@@ -15,12 +15,13 @@
 //                       M = sample in frame (1024, in two halves: a workgroup has 512 rows), N = frame (64), K = packed real spectrum
 //                       (1024).  The inverse basis (hann[n] c_b cos / -sin (2 pi b n / 1024) / 1024, c_b = 1 for bins 0 and 512, else 2)
 //                       streams from L2 to registers in lane order
-//                       like the forward basis; the spectrum tile (256 KB) does not fit LDS, so K runs in four chunks of 256 staged at
+//                       like the forward basis (stft.h: the same product); the spectrum tile (256 KB) does not fit LDS, so K runs in four chunks of 256 staged at
 //                       257 floats per frame (conflict-free B reads).
-//   gl_forward_kernel   windowed frames -> next spectrum state: the front-end's product with another loader and epilogue.  The loader
-//                       builds every padded sample of the tile as the sum of the at most 4 frame pieces that cover it, in ascending frame
-//                       order, over the envelope (the reflection is index arithmetic before that); the epilogue has (re, im) of one
-//                       (bin, frame) in one lane: momentum term from the stored R_k-1, normalise, times M, store M A_k+1 and R_k.
+//   gl_forward_kernel   windowed frames -> next spectrum state: the front-end's product with another loader and epilogue, literally --
+//                       the tile, the reflected staging and the product are the code of stft.h that audio_log_mel_kernel runs, on the
+//                       front-end's own operand.  The loader's sample is the sum of the at most 4 frame pieces that cover it, in
+//                       ascending frame order, over the envelope; the epilogue has (re, im) of one (bin, frame) in one lane: momentum
+//                       term from the stored R_k-1, normalise, times M, store M A_k+1 and R_k.
 //   gl_overlap_add_kernel  the loader's overlap-add on its own, for the waveform.
 //
 // Packed spectrum of a frame ([1024] floats): (re, im) of bins 0..511 with the real part of bin 512 in the slot of bin 0's imaginary
@@ -28,8 +29,8 @@
 //
 // Workspace: spectrum [F][1024] | R [F][1024] | frames [F][1024] | M [F][514], F = B T.
 #include "mcvc_common.h"
-#include "audio.h"
 #include "griffinlim.h"
+#include "stft.h"
 #include "trace.h"
 
 #include <cmath>
@@ -38,16 +39,13 @@
 
 namespace {
 
-constexpr int HOP = MCVC_AUDIO_HOP, NFFT = MCVC_AUDIO_NFFT, PAD = (NFFT - HOP) / 2, NBIN = NFFT / 2 + 1, NMEL = MCVC_AUDIO_NMEL;
-constexpr int TF = MCVC_AUDIO_TILE_FRAMES;                 // frames per workgroup
-constexpr int SPAN = (TF - 1) * HOP + NFFT;                // samples the frames of a tile cover
-constexpr int SPAN_LDS = SPAN + SPAN / 256 + 1;            // one float of skew per 256: frame n starts at 257 n
-constexpr int KG = NFFT / 8;                               // k groups of 8 (one 16-byte basis load per lane and row tile)
-constexpr int KCHUNK = 256, CHUNK_LDS = TF * (KCHUNK + 1); // inverse kernel: K staged 256 at a time, 257 floats per frame
-constexpr int NTHREADS = 512, MT_PER_WAVE = 2, M_SPLIT = 2; // eight waves x two row tiles = half of the 32 row tiles; blockIdx.y has the half
-constexpr int FLUSH_KG = 4;                                // k groups (32 terms) summed from zero before they join the running total
+using namespace stft;
+
+constexpr int KCHUNK = 256, CHUNK_LDS = TF * PITCH;        // inverse kernel: K staged 256 at a time, 257 floats per frame
+static_assert(KCHUNK + 1 == PITCH && NFFT % KCHUNK == 0, "a chunk is staged at the pitch stft_product reads");
+constexpr int MT_PER_WAVE = 2, M_SPLIT = 2;                // eight waves x two row tiles = half of the 32 row tiles; blockIdx.y has the half
+constexpr int FLUSH_KG = 4;                                // k groups (32 terms) summed from zero before they join the running total (stft_product)
 constexpr int MAG_LD = NBIN + 1;                           // M rows of 514: pairs of bins are 8-byte aligned
-constexpr long long DFT_FLOATS = (long long)NFFT * NFFT;
 constexpr long long OFF_PINV = DFT_FLOATS, OFF_W2 = OFF_PINV + (long long)NBIN * NMEL, OFF_FWD = OFF_W2 + NFFT;
 static_assert(OFF_W2 % 4 == 0 && OFF_FWD % 4 == 0, "16-byte aligned table sections");
 
@@ -111,58 +109,6 @@ __global__ void __launch_bounds__(256) gl_init_kernel(const GlArgs a)
     }
 }
 
-// tot[mt][nt] += row tiles mt of a lane-ordered basis (ap: the wave's first) x the 64 columns staged at 257 floats each, k groups kg0 ..
-// kg0 + nkg - 1 (b_lane0: the lane's column base for the FIRST of those groups; SKEW: the stage keeps one float of skew per 256 k).
-// An MFMA chain is a k-ordered fmaf chain: a straight sum of 1024 terms is ~3.6x further from float64 than an FFT (measured: 5.7e-7
-// against 1.5e-7 rel-L2 for one inverse transform).  So every 32 terms are summed from zero in accumulators of their own and then added
-// to the running total -- chains of 32 + 32 instead of 1024, the two levels of the decoder's GEMM.
-template <bool SKEW>
-__device__ __forceinline__ void gl_product(f32x16 (&tot)[MT_PER_WAVE][2], const f32x4* __restrict__ ap, const float* b_lane0, int kg0, int nkg)
-{
-    const float* const b_lane1 = b_lane0 + 257 * 32;
-    f32x4 st0[MT_PER_WAVE], st1[MT_PER_WAVE];
-    f32x16 acc[MT_PER_WAVE][2];
-    auto fetch = [&](f32x4 (&st)[MT_PER_WAVE], int kg) {
-#pragma unroll
-        for (int mt = 0; mt < MT_PER_WAVE; ++mt) st[mt] = ap[((long long)mt * KG + kg) * 64];
-    };
-    auto multiply = [&](const f32x4 (&st)[MT_PER_WAVE], int kl) {
-        const int kb = 8 * kl + (SKEW ? (kl >> 5) : 0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float b0 = b_lane0[kb + 2 * j], b1 = b_lane1[kb + 2 * j];
-#pragma unroll
-            for (int mt = 0; mt < MT_PER_WAVE; ++mt) {
-                acc[mt][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(st[mt][j], b0, acc[mt][0], 0, 0, 0);
-                acc[mt][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(st[mt][j], b1, acc[mt][1], 0, 0, 0);
-            }
-        }
-    };
-    fetch(st0, kg0);
-#pragma unroll 1
-    for (int kf = 0; kf < nkg; kf += FLUSH_KG) {
-#pragma unroll
-        for (int mt = 0; mt < MT_PER_WAVE; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
-#pragma unroll
-        for (int kl = kf; kl < kf + FLUSH_KG; kl += 2) {
-            fetch(st1, kg0 + kl + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            multiply(st0, kl);
-            fetch(st0, kl + 2 < nkg ? kg0 + kl + 2 : kg0 + kl);    // (the last one is a repeat nobody uses)
-            __builtin_amdgcn_sched_barrier(0);
-            multiply(st1, kl + 1);
-        }
-#pragma unroll
-        for (int mt = 0; mt < MT_PER_WAVE; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) tot[mt][nt] += acc[mt][nt];
-    }
-}
-
 __global__ void __launch_bounds__(NTHREADS) gl_inverse_kernel(const GlArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -176,12 +122,7 @@ __global__ void __launch_bounds__(NTHREADS) gl_inverse_kernel(const GlArgs a)
     const long long f0 = (long long)b * T + t0;
 
     f32x16 acc[MT_PER_WAVE][2];
-#pragma unroll
-    for (int mt = 0; mt < MT_PER_WAVE; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
+    stft_zero(acc);
     const int rt0 = (blockIdx.y * (NTHREADS / 64) + wave) * MT_PER_WAVE;     // the wave's first row tile
     const f32x4* const ap = reinterpret_cast<const f32x4*>(a.tables) + (long long)rt0 * KG * 64 + lane;
     const f32x4* const sp = reinterpret_cast<const f32x4*>(a.spec);
@@ -192,24 +133,23 @@ __global__ void __launch_bounds__(NTHREADS) gl_inverse_kernel(const GlArgs a)
             const int n = i >> 6, q = i & 63;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (n < nv) v = sp[(f0 + n) * (NFFT / 4) + c * (KCHUNK / 4) + q];
-            float* d = smem + 257 * n + 4 * q;
+            float* d = smem + PITCH * n + 4 * q;
             d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
         }
         __syncthreads();
-        gl_product<false>(acc, ap, smem + 257 * l31 + half, c * (KCHUNK / 8), KCHUNK / 8);
+        stft_product<MT_PER_WAVE, FLUSH_KG, false>(acc, ap, stft_b_lane(smem, l31, half), c * (KCHUNK / 8), KCHUNK / 8);
     }
-    // accumulator row 8 q + 4 half + i of row tile rt0 + mt is sample 32 (rt0 + mt) + that of frame l31 + 32 nt
+    // a basis row is a sample of the frame: row 2 p is sample 2 p
 #pragma unroll
     for (int mt = 0; mt < MT_PER_WAVE; ++mt)
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-            const int n = l31 + 32 * nt;
+            const int n = stft_col(l31, nt);
             if (n >= nv) continue;
-            f32x4* const dst = reinterpret_cast<f32x4*>(a.frames + (f0 + n) * NFFT + 32 * (rt0 + mt) + 4 * half);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 f32x4 v = {acc[mt][nt][4 * q], acc[mt][nt][4 * q + 1], acc[mt][nt][4 * q + 2], acc[mt][nt][4 * q + 3]};
-                dst[2 * q] = v;
+                *reinterpret_cast<f32x4*>(a.frames + (f0 + n) * NFFT + 2 * stft_pair(rt0 + mt, q, half)) = v;
             }
         }
 }
@@ -231,31 +171,13 @@ __global__ void __launch_bounds__(NTHREADS) gl_forward_kernel(const GlArgs a)
     // ---- the tile's samples: x = the overlap-add cropped to [384, 384 + 256 T), reflected at its own two ends ----
     const float* const fr = a.frames + (long long)b * T * NFFT;
     const float* const w2 = a.tables + OFF_W2;
-    const int L = HOP * T;
-    const int p0 = t0 * HOP - PAD;
-    const int s_end = (nv - 1) * HOP + NFFT;
-    for (int s = tid; s < SPAN; s += NTHREADS) {
-        float v = 0.f;
-        if (s < s_end) {
-            int i = p0 + s;
-            if (i < 0) i = -i;
-            if (i >= L) i = 2 * (L - 1) - i;
-            if (i >= 0 && i < L) v = gl_ola(fr, w2, T, i + PAD);    // (always true: L >= 512 > 384)
-        }
-        smem[s + (s >> 8)] = v;
-    }
-    __syncthreads();
+    stft_stage_tile(smem, t0, nv, HOP * T, [&](int i) { return gl_ola(fr, w2, T, i + PAD); });
 
     f32x16 acc[MT_PER_WAVE][2];
-#pragma unroll
-    for (int mt = 0; mt < MT_PER_WAVE; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
+    stft_zero(acc);
     const int rt0 = (blockIdx.y * (NTHREADS / 64) + wave) * MT_PER_WAVE;     // the wave's first row tile
     const f32x4* const ap = reinterpret_cast<const f32x4*>(a.tables + OFF_FWD) + (long long)rt0 * KG * 64 + lane;
-    gl_product<true>(acc, ap, smem + 257 * l31 + half, 0, KG);
+    stft_product<MT_PER_WAVE, FLUSH_KG, true>(acc, ap, stft_b_lane(smem, l31, half), 0, KG);
 
     // ---- update: rows (2 pr, 2 pr + 1) of a lane are (sum x hann cos, sum x hann sin) = (Re, -Im) of one (bin, frame) ----
     const float c = a.coef;
@@ -267,12 +189,12 @@ __global__ void __launch_bounds__(NTHREADS) gl_forward_kernel(const GlArgs a)
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-            const int n = l31 + 32 * nt;
+            const int n = stft_col(l31, nt);
             if (n >= nv) continue;
             const long long f = f0 + n;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int bin = 16 * (rt0 + mt) + 4 * q + 2 * half;                      // this lane holds bins (bin, bin + 1)
+                const int bin = stft_pair(rt0 + mt, q, half);                         // this lane holds bins (bin, bin + 1)
                 const long long at = f * (NFFT / 4) + (bin >> 1);
                 f32x4 pv = {0.f, 0.f, 0.f, 0.f};
                 if (!a.first) pv = pv4[at];
@@ -308,8 +230,6 @@ __global__ void __launch_bounds__(256) gl_overlap_add_kernel(const GlArgs a)
     a.out[(long long)b * L + i] = gl_ola(a.frames + (long long)b * T * NFFT, a.tables + OFF_W2, T, i + PAD);
 }
 
-const double kPi = 3.14159265358979323846;
-
 bool shape_ok(int B, int T)
 {
     return B >= 1 && T >= MCVC_GL_MIN_FRAMES && T <= MCVC_GL_MAX_FRAMES && (long long)B * T <= (1LL << 22) && B <= 65535;
@@ -325,29 +245,19 @@ long long mcvc_gl_tables_floats_of() { return OFF_FWD + mcvc_audio_basis_floats_
 
 void mcvc_gl_tables_fill(const float* pinv, float* out)
 {
-    std::vector<double> hann(NFFT), cs(NFFT), sn(NFFT);
-    for (int k = 0; k < NFFT; ++k) {
-        hann[k] = 0.5 - 0.5 * std::cos(2.0 * kPi * k / NFFT);             // periodic (torch.hann_window)
-        cs[k] = std::cos(2.0 * kPi * k / NFFT);
-        sn[k] = std::sin(2.0 * kPi * k / NFFT);
-    }
-    // float index ((mt * 128 + kg) * 64 + lane) * 4 + j  =  IB[sample n = 32 mt + (lane & 31)][packed spectrum slot k = 8 kg + 2 j + (lane >> 5)]
-    for (int mt = 0; mt < NFFT / 32; ++mt)
-        for (int kg = 0; kg < KG; ++kg)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 4; ++j) {
-                    const int k = 8 * kg + 2 * j + (lane >> 5), n = 32 * mt + (lane & 31);
-                    double v;
-                    if (k == 0) v = 1.0;                                   // bin 0
-                    else if (k == 1) v = (n & 1) ? -1.0 : 1.0;             // bin 512: cos(pi n)
-                    else {
-                        const int ph = (int)(((long long)n * (k >> 1)) % NFFT);     // exact argument reduction
-                        v = (k & 1) ? -2.0 * sn[ph] : 2.0 * cs[ph];
-                    }
-                    out[(((long long)mt * KG + kg) * 64 + lane) * 4 + j] = (float)(hann[n] * v / NFFT);
-                }
+    const Tables w;
+    stft_fill_lane_order(out, [&](int k, int n) {           // IB[sample n][packed spectrum slot k]
+        double v;
+        if (k == 0) v = 1.0;                                // bin 0
+        else if (k == 1) v = (n & 1) ? -1.0 : 1.0;          // bin 512: cos(pi n)
+        else {
+            const int ph = stft_phase(n, k >> 1);
+            v = (k & 1) ? -2.0 * w.sn[ph] : 2.0 * w.cs[ph];
+        }
+        return w.hann[n] * v / NFFT;
+    });
     for (int i = 0; i < NBIN * NMEL; ++i) out[OFF_PINV + i] = pinv[i];
-    for (int k = 0; k < NFFT; ++k) out[OFF_W2 + k] = (float)(hann[k] * hann[k]);
+    for (int k = 0; k < NFFT; ++k) out[OFF_W2 + k] = (float)(w.hann[k] * w.hann[k]);
     mcvc_audio_basis_fill(out + OFF_FWD);
 }
 

@@ -147,28 +147,20 @@ class Audio2Mel(object):
     (the convention of the reference's ``vocoder.fft``), and ``fft.bank(waveforms)`` for utterances of different lengths:
     one launch, one float32 [80, T_i] array per utterance."""
 
-    _basis = {}                                                        # device index -> the constant operand, uploaded once
-
     def __init__(self, device=None):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("data_preprocessing.audio2mel (MI355X build) needs a HIP device; there is no CPU path")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("data_preprocessing.audio2mel (MI355X build): device must be a HIP device; there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        from mask_cyclegan_vc._hip import hip_device
+        self.device = hip_device("data_preprocessing.audio2mel", device)
 
     def basis(self):
-        import torch
-        from mask_cyclegan_vc._hip import check, lib
-        t = Audio2Mel._basis.get(self.device.index)
-        if t is None:
+        """The constant operand (``mcvc_audio_basis_init``), uploaded once per device."""
+        from mask_cyclegan_vc._hip import check, device_constant, lib
+
+        def host_basis():
             L = lib()
             host = np.empty(L.mcvc_audio_basis_floats(), dtype=np.float32)
             check(L.mcvc_audio_basis_init(host.ctypes.data), "mcvc_audio_basis_init")
-            t = Audio2Mel._basis[self.device.index] = torch.from_numpy(host).to(self.device)
-        return t
+            return host
+        return device_constant("audio2mel.basis", self.device, host_basis)
 
     def _launch(self, wave, lengths):
         """wave: contiguous float32 device tensor holding the utterances back to back -> ([80, total_frames] device tensor, frame offsets)."""
@@ -199,16 +191,14 @@ class Audio2Mel(object):
 
     def __call__(self, x):
         import torch
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise RuntimeError("data_preprocessing.audio2mel (MI355X build): tensors must live on a HIP device; there is no CPU path")
+        from mask_cyclegan_vc._hip import require_on_device
+        require_on_device("data_preprocessing.audio2mel", x, self.device, "waveform", "front-end")
         if x.dim() == 3 and x.shape[1] == 1:
             x = x[:, 0]
         if x.dim() != 2:
             raise ValueError("expected a [B, 1, L] or [B, L] waveform tensor, got %s" % (tuple(x.shape),))
         B, n = x.shape
         T = num_frames(n)
-        if x.device != self.device:
-            raise RuntimeError("waveform on %s, front-end on %s" % (x.device, self.device))
         wave = x.to(torch.float32).contiguous()
         out, _ = self._launch(wave, [n] * B)
         return out.view(N_MEL, B, T).permute(1, 0, 2).contiguous()

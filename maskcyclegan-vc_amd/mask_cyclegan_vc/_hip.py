@@ -215,6 +215,39 @@ def ptr_table(tensors):
     return arr
 
 
+def hip_device(module_name, device=None):
+    """``device`` (default: the current one) as a ``torch.device`` with its index filled in; raises in ``module_name``'s name where
+    there is no HIP device or ``device`` is not one."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("%s (MI355X build) needs a HIP device; there is no CPU path" % module_name)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("%s (MI355X build): device must be a HIP device; there is no CPU path" % module_name)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+def require_on_device(module_name, t, device, what, owner):
+    """``t`` (the caller's ``what``) must be a tensor on ``device``, the HIP device of the caller's ``owner``."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("%s (MI355X build): tensors must live on a HIP device; there is no CPU path" % module_name)
+    if t.device != device:
+        raise RuntimeError("%s on %s, %s on %s" % (what, t.device, owner, device))
+
+
+_constants = {}                       # (cache key, device index) -> a constant operand, uploaded once
+
+
+def device_constant(cache_key, device, build_host):
+    """The constant operand ``cache_key`` on ``device``: ``build_host()`` makes it as a numpy array, once per device."""
+    key = (cache_key, device.index)
+    t = _constants.get(key)
+    if t is None:
+        t = _constants[key] = torch.from_numpy(build_host()).to(device)
+    return t
+
+
 def require_cuda_f32(*ts):
     for t in ts:
         if t is None:

@@ -54,16 +54,8 @@ class GriffinLimVocoder(object):
     """``GriffinLimVocoder(device=None, n_iter=32, momentum=0.99, seed=0)``; then ``inverse(mel)``, ``from_magnitude(mag)`` and
     ``__call__(audio)``."""
 
-    _tables = {}                                                       # device index -> the constant operand, uploaded once
-
     def __init__(self, device=None, n_iter=32, momentum=0.99, seed=0):
-        if not torch.cuda.is_available():
-            raise RuntimeError("mask_cyclegan_vc.griffinlim (MI355X build) needs a HIP device; there is no CPU path")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("mask_cyclegan_vc.griffinlim (MI355X build): device must be a HIP device; there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _hip.hip_device("mask_cyclegan_vc.griffinlim", device)
         if int(n_iter) < 0:
             raise ValueError("n_iter must be >= 0, got %r" % (n_iter,))
         if not 0.0 <= float(momentum) < 1.0:
@@ -72,10 +64,7 @@ class GriffinLimVocoder(object):
         self._fft = None
 
     def tables(self):
-        t = GriffinLimVocoder._tables.get(self.device.index)
-        if t is None:
-            t = GriffinLimVocoder._tables[self.device.index] = torch.from_numpy(host_tables()).to(self.device)
-        return t
+        return _hip.device_constant("griffinlim.tables", self.device, host_tables)
 
     def angles(self, B, T):
         """The initial angles of a [B, ., T] call as (re, im) float32 [B, 513, T, 2]: one seeded draw of [513, T], the same for every sample."""
@@ -87,8 +76,7 @@ class GriffinLimVocoder(object):
             return one[None].expand(B, N_BIN, T, 2).contiguous()
 
     def _decode(self, x, kind, rows, angles, n_iter, momentum):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise RuntimeError("mask_cyclegan_vc.griffinlim (MI355X build): tensors must live on a HIP device; there is no CPU path")
+        _hip.require_on_device("mask_cyclegan_vc.griffinlim", x, self.device, "input", "decoder")
         if x.dim() != 3 or x.shape[1] != rows:
             raise ValueError("expected a [B, %d, T] tensor, got %s" % (rows, tuple(x.shape)))
         B, _, T = x.shape
@@ -96,8 +84,6 @@ class GriffinLimVocoder(object):
             raise ValueError("the Griffin-Lim decoder needs at least %d frames (reflect padding of 384 samples), got %d" % (MIN_FRAMES, T))
         if B < 1:
             raise ValueError("empty batch")
-        if x.device != self.device:
-            raise RuntimeError("input on %s, decoder on %s" % (x.device, self.device))
         n_iter = self.n_iter if n_iter is None else int(n_iter)
         momentum = self.momentum if momentum is None else float(momentum)
         if n_iter < 0 or not 0.0 <= momentum < 1.0:

@@ -48,8 +48,6 @@ MAX_K = 80
 TABLE_COLS = 6
 MCD_SCALE = (10.0 / math.log(10.0)) * math.sqrt(2.0)
 
-_basis = {}                                                            # (device index, n_cep) -> the constant operand, uploaded once
-
 
 def dct_basis(n_cep):
     """float64 [n_cep, 80]: rows 1 .. n_cep of the orthonormal DCT-II over the 80 mel bins."""
@@ -75,27 +73,13 @@ def max_frames():
     return int(_hip.lib().mcvc_dtw_max_frames())
 
 
-def _device(device=None):
-    if not torch.cuda.is_available():
-        raise RuntimeError("mask_cyclegan_vc.metrics (MI355X build) needs a HIP device; there is no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("mask_cyclegan_vc.metrics (MI355X build): device must be a HIP device; there is no CPU path")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
-
-
 def bank(feats, device=None, rows=None):
     """list of [K, T_i] (tensors or arrays) or ``(bank, offs)`` -> (float32 device tensor [K, N], int32 numpy offsets [n + 1]).
     Shapes, finiteness and the device are checked here."""
-    dev = _device(device)
+    dev = _hip.hip_device("mask_cyclegan_vc.metrics", device)
     if isinstance(feats, tuple) and len(feats) == 2 and isinstance(feats[0], torch.Tensor) and feats[0].dim() == 2 and not isinstance(feats[1], torch.Tensor):
         b, offs = feats
-        if not b.is_cuda:
-            raise RuntimeError("mask_cyclegan_vc.metrics (MI355X build): tensors must live on a HIP device; there is no CPU path")
-        if b.device != dev:
-            raise RuntimeError("bank on %s, metrics on %s" % (b.device, dev))
+        _hip.require_on_device("mask_cyclegan_vc.metrics", b, dev, "bank", "metrics")
         offs = np.ascontiguousarray(offs, dtype=np.int64).reshape(-1)
         if offs.size < 2 or offs[0] != 0 or offs[-1] != b.shape[1] or bool((np.diff(offs) < 1).any()):
             raise ValueError("offsets must rise from 0 to the bank's %d frames" % b.shape[1])
@@ -182,10 +166,7 @@ def mel_cepstra(mels, n_cep=24):
     if not 1 <= n_cep <= N_MEL - 1:
         raise ValueError("n_cep must lie in 1 .. %d, got %r" % (N_MEL - 1, n_cep))
     dev = b.device
-    key = (dev.index, n_cep)
-    basis = _basis.get(key)
-    if basis is None:
-        basis = _basis[key] = torch.from_numpy(host_basis(n_cep)).to(dev)
+    basis = _hip.device_constant(("metrics.dct_basis", n_cep), dev, lambda: host_basis(n_cep))
     with torch.no_grad(), torch.cuda.device(dev):
         out = torch.empty(n_cep, b.shape[1], dtype=torch.float32, device=dev)
         _hip.check(_hip.lib().mcvc_cep_project(_hip.ptr(b), b.shape[1], _hip.ptr(basis), n_cep, _hip.ptr(out), _hip.stream()), "mcvc_cep_project")
@@ -220,7 +201,7 @@ def f0_stats(f0_x, f0_y, paths):
     """F0 tracks (lists of [T_i], 0 = unvoiced) and the pairs' warping paths (list of int32 [length_p, 2], as ``dtw(..., return_path=True)``
     returns them) -> dict of numpy arrays over the pairs: ``rmse_cents``, ``bias_cents`` (float64; nan where ``voiced_pairs`` is 0),
     ``vuv_error``, ``voiced_pairs``, ``length``, and the raw ``counts`` [n, 4] (both voiced, x only, y only, neither).  One launch."""
-    dev = _device()
+    dev = _hip.hip_device("mask_cyclegan_vc.metrics")
     f0_x, f0_y, paths = list(f0_x), list(f0_y), list(paths)
     n = len(paths)
     if n < 1 or len(f0_x) != n or len(f0_y) != n:

@@ -31,7 +31,6 @@ import numpy as np
 import torch
 
 from . import _hip
-from .metrics import _device
 
 SAMPLING_RATE = 22050
 HOP_LENGTH = 256
@@ -66,7 +65,7 @@ class PitchTracker(object):
         self.fmin, self.fmax = float(fmin), float(fmax)
         self._lags = lag_range(fmin, fmax)
         self.threshold = check_threshold(threshold)
-        self.device = _device(device)
+        self.device = _hip.hip_device("mask_cyclegan_vc.metrics", device)                # (the name these messages have always carried)
 
     @property
     def lags(self):
@@ -77,10 +76,7 @@ class PitchTracker(object):
         -> (f0 [N], aperiodicity [N], frame_offs int32 numpy [n + 1][, cmnd [tau_max + 1, N]]) on the current stream; utterance u owns
         frames frame_offs[u] .. frame_offs[u + 1].  ``cmnd`` holds the d' values the pick was made on."""
         from data_preprocessing.audio2mel import plan_bank
-        if not isinstance(wave, torch.Tensor) or not wave.is_cuda:
-            raise RuntimeError("mask_cyclegan_vc.pitch (MI355X build): tensors must live on a HIP device; there is no CPU path")
-        if wave.device != self.device:
-            raise RuntimeError("waveform on %s, tracker on %s" % (wave.device, self.device))
+        _hip.require_on_device("mask_cyclegan_vc.pitch", wave, self.device, "waveform", "tracker")
         if wave.dtype != torch.float32 or not wave.is_contiguous() or wave.dim() != 1:
             raise ValueError("expected a contiguous 1-D float32 tensor of samples")
         lengths = [int(k) for k in lengths]

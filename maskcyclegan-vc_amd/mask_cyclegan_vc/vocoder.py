@@ -102,13 +102,7 @@ class MelVocoder(object):
     """``MelVocoder().load_state_dict(sd)`` / ``MelVocoder.from_checkpoint(path)``; then ``inverse(mel)`` and ``__call__(audio)``."""
 
     def __init__(self, device=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("mask_cyclegan_vc.vocoder (MI355X build) needs a HIP device; there is no CPU path")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("mask_cyclegan_vc.vocoder (MI355X build): device must be a HIP device; there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _hip.hip_device("mask_cyclegan_vc.vocoder", device)
         self.packed = None
         self._fft = None
 
@@ -134,8 +128,7 @@ class MelVocoder(object):
         """[B, 80, T] log10-mel on the HIP device -> [B, 256 T] float32 waveform; one batched decode on the current stream."""
         if self.packed is None:
             raise RuntimeError("MelVocoder: no weights loaded (load_state_dict / from_checkpoint)")
-        if not isinstance(mel, torch.Tensor) or not mel.is_cuda:
-            raise RuntimeError("mask_cyclegan_vc.vocoder (MI355X build): tensors must live on a HIP device; there is no CPU path")
+        _hip.require_on_device("mask_cyclegan_vc.vocoder", mel, self.device, "mel", "vocoder")
         if mel.dim() != 3 or mel.shape[1] != N_MEL:
             raise ValueError("expected a [B, 80, T] mel tensor, got %s" % (tuple(mel.shape),))
         B, _, T = mel.shape
@@ -143,8 +136,6 @@ class MelVocoder(object):
             raise ValueError("the MelGAN decoder needs at least %d frames (ReflectionPad1d(3)), got %d" % (MIN_FRAMES, T))
         if B < 1:
             raise ValueError("empty batch")
-        if mel.device != self.device:
-            raise RuntimeError("mel on %s, vocoder on %s" % (mel.device, self.device))
         L = _hip.lib()
         with torch.no_grad(), torch.cuda.device(self.device):
             x = mel.detach().to(torch.float32).contiguous()

@@ -45,6 +45,35 @@ def test_library_mel_table_is_the_same_basis():
     assert np.array_equal(B, audio2mel.mel_filterbank())
 
 
+def test_forward_basis_fill_against_numpy():
+    """W[row][k], the lane order undone: rows 2b / 2b + 1 = hann[k] cos / sin(2 pi k b / 1024) of bin b = 1..511, row 0 the window itself
+    (bin 0) and row 1 the Nyquist cosine hann[k] (-1)^k -- the sines of bins 0 and 512 are zero and have no row."""
+    L = _hip.lib()
+    N = 1024
+    host = np.empty(L.mcvc_audio_basis_floats(), dtype=np.float32)
+    assert L.mcvc_audio_basis_init(host.ctypes.data) == 0
+    # float index ((mt * 128 + kg) * 64 + 32 half + l31) * 4 + j  ->  W[row 32 mt + l31][k = 8 kg + 2 j + half]
+    W = host[:N * N].reshape(32, 128, 2, 32, 4).transpose(0, 3, 1, 4, 2).reshape(N, N).astype(np.float64)
+    k = np.arange(N)
+    w = 0.5 - 0.5 * np.cos(2.0 * np.pi * k / N)
+    want = np.zeros((N, N))
+    want[0] = w
+    want[1] = w * np.where(k % 2 == 0, 1.0, -1.0)
+    for b in range(1, 512):
+        ph = 2.0 * np.pi * ((k * b) % N) / N                   # exact argument reduction
+        want[2 * b] = w * np.cos(ph)
+        want[2 * b + 1] = w * np.sin(ph)
+    err = float(np.abs(W - want).max())
+    print("forward basis: max abs difference %.3e (one float32 ulp of the largest entry: %.3e)" % (err, 2.0 ** -23))
+    assert err <= 2.0 ** -23                                    # the inverse fill's rule: float32 rounding of values up to 1, cos / sin of two libraries
+    # as an operator: the basis applied to a frame gives the packed rfft of the windowed frame, (Re, -Im) per bin
+    x = np.random.RandomState(0).randn(N)
+    S = np.fft.rfft(w * x)
+    packed = np.zeros(N)
+    packed[0], packed[1], packed[2::2], packed[3::2] = S[0].real, S[512].real, S[1:512].real, -S[1:512].imag
+    assert np.abs(W @ x - packed).max() <= 2.0 ** -23 * np.abs(x).sum()      # every basis entry within one float32 ulp of 1
+
+
 def test_frame_count_law():
     L = _hip.lib()
     for n in (0, 1, 384):
