@@ -436,6 +436,40 @@ int mcvc_f0_track(const float* wave, long long n_samples, const int* tiles, int 
 int mcvc_f0_stats(const float* fx, long long x_frames, const float* fy, long long y_frames, const int* path, const long long* pairs, int n_pairs,
                   int* counts, float* sums, void* stream);
 
+/* ---- non-parallel evaluation (new): modulation spectra, global variance and the distance between two SETS of utterances
+ *      (csrc/ms_kernels.hip; mask_cyclegan_vc/metrics.py and INTEGRATION.md restate this).  cep is a cepstra bank [K][n_frames] fp32 with
+ *      offsets offs[n_utts + 1], as mcvc_cep_project fills it; 1 <= K <= 80; utterance u has T frames, T <= n_fft; n_fft is 1024, 2048 or 4096.
+ *      Per utterance and row k:  mean = (1/T) sum_t c[k][t];  x[t] = c[k][t] - mean;  var = (1/T) sum_t x[t]^2 (population variance, from the
+ *      deviations);  X[f] = sum_{t < T} x[t] exp(-2 pi i f t / n_fft), f = 1 .. n_fft / 2 (rectangular window zero-padded to n_fft; bin 0 is
+ *      dropped, the mean was removed);  P[u][k][f - 1] = |X[f]|^2 / T.  Bin f lies at f (22050 / 256) / n_fft Hz.
+ *      Twiddles: a table of cos(2 pi j / n_fft), j < n_fft, float64 rounded once, read at the INTEGER phase (f t) mod n_fft (exact argument
+ *      reduction; the phase is never formed in floating point); the sine is the same table a quarter turn on.
+ *      Per set of n utterances, floor = 1e-10 by definition:  LMS[k][f] = (1/n) sum_u 10 log10(max(P[u][k][f], floor)) dB and
+ *      LGV[k] = (1/n) sum_u 10 log10(max(var[u][k], floor)) dB, utterances summed in index order.  Between two sets, over the first F bins:
+ *      msd_per_dim[k] = sqrt((1/F) sum_f (LMS_A - LMS_B)^2), msd = sqrt((1/(K F)) sum_{k,f} (..)^2), gvd = sqrt((1/K) sum_k (LGV_A - LGV_B)^2).
+ *      No atomics, every reduction in a fixed order; an utterance's P, mean and var depend on that utterance alone: a ragged batch equals its
+ *      single calls bit for bit.  All calls are asynchronous on `stream`, allocate nothing on the device and launch nothing when they refuse.
+ *        mcvc_ms_max_fft      4096 (= mcvc_dtw_max_frames()): the largest n_fft and the longest utterance.
+ *        mcvc_ms_launches     kernel launches of one MSD + GVD evaluation of two sets from their cepstra banks: 8 (2 x mcvc_ms_power,
+ *                             4 x mcvc_ms_mean_log for P and var of both sets, 2 x mcvc_ms_distance).
+ *        mcvc_ms_table_init   HOST buffer [n_fft]: cos(2 pi j / n_fft).  The caller uploads it (16-byte aligned) once per device and n_fft.
+ *        mcvc_ms_power        one launch for the whole bank.  cep, offs_dev (int32 [n_utts + 1]), table, power [n_utts][K][n_fft / 2], mean and
+ *                             var [n_utts][K] are DEVICE pointers; offs_host is the same offset table on the HOST, validated here.
+ *                             MCVC_ERR_INVALID: a null or misaligned pointer (4 bytes; table: 16), K outside 1 .. 80, an n_fft other than
+ *                             the three, n_utts < 1, offsets that do not rise from 0 to n_frames, an utterance longer than n_fft.
+ *        mcvc_ms_mean_log     values [n][R] -> out [R] = (1/n) sum_u 10 log10(max(values[u][r], floor)).  MCVC_ERR_INVALID: a null or misaligned
+ *                             pointer, n < 1, R < 1, a floor that is not positive and finite.
+ *        mcvc_ms_distance     a, b [K][n_bins] -> per_dim [K], total [1] over the first n_used bins of every row; one workgroup, fixed-order
+ *                             trees.  GVD is the call with the [K] tables as one row of K bins.  MCVC_ERR_INVALID: a null or misaligned
+ *                             pointer, K outside 1 .. 80, n_bins outside 1 .. 2048, n_used outside 1 .. n_bins.                         */
+int mcvc_ms_max_fft(void);
+int mcvc_ms_launches(void);
+int mcvc_ms_table_init(int n_fft, float* table_host);
+int mcvc_ms_power(const float* cep, long long n_frames, int K, const int* offs_dev, int n_utts, const int* offs_host, int n_fft, const float* table,
+                  float* power, float* mean, float* var, void* stream);
+int mcvc_ms_mean_log(const float* values, int n, long long R, float floor, float* out, void* stream);
+int mcvc_ms_distance(const float* a, const float* b, int K, int n_bins, int n_used, float* per_dim, float* total, void* stream);
+
 /* ---- single-op entry points (kernel parity tests; same kernels the network calls use) ---------- */
 /* y[N,Cout,OH,OW] = conv2d(x[N,Cin,H,W], w[Cout,Cin,KH,KW]) + bias ; stride 1 or 2.
  * wpack: scratch of mcvc_conv2d_pack_floats() floats, zero-initialised by the caller.

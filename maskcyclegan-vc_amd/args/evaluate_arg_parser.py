@@ -25,6 +25,15 @@ class EvaluateArgParser(object):
         ("--f0_min", dict(type=float, default=60.0, help="With --f0: lowest F0 searched, Hz (longest lag floor(22050 / f0_min) <= 640).")),
         ("--f0_max", dict(type=float, default=500.0, help="With --f0: highest F0 searched, Hz (shortest lag ceil(22050 / f0_max) >= 2).")),
         ("--f0_threshold", dict(type=float, default=0.15, help="With --f0: YIN's threshold on the normalised difference function, in (0, 1].")),
+        ("--msd", dict(action="store_true", help="Also report the modulation-spectrum distance (MSD) and the global-variance distance (GVD), in dB, of "
+                       "ALL converted utterances against ALL of the target speaker's: two sets, no alignment, no parallel sentences needed "
+                       "(mask_cyclegan_vc/metrics.py msd).")),
+        ("--msd_n_fft", dict(type=int, default=4096, choices=(1024, 2048, 4096), help="With --msd: length the mean-removed cepstral trajectories are "
+                             "zero-padded to; no utterance may be longer.")),
+        ("--msd_max_hz", dict(type=float, default=None, help="With --msd: compare the modulation bins at or below this frequency only "
+                              "(default: all, up to Nyquist = 43.07 Hz).")),
+        ("--no_mcd", dict(action="store_true", help="For a corpus without parallel sentences: skip MCD, its baseline and the rule that reference i is the "
+                          "sentence of converted utterance i.  Needs --msd; not with --f0.")),
     ]
 
     def __init__(self):
@@ -40,6 +49,16 @@ class EvaluateArgParser(object):
             self.parser.error("--n_cep takes a number of coefficients in 1 .. 79")
         if args.f0 and args.target_wav_dir is None:
             self.parser.error("--f0 needs the references as audio: give --target_wav_dir (preprocessed caches hold no waveforms)")
+        if args.no_mcd and not args.msd:
+            self.parser.error("--no_mcd leaves nothing to report: give --msd with it")
+        if args.no_mcd and args.f0:
+            self.parser.error("--f0 runs along the DTW alignment that --no_mcd skips: give one of the two")
+        if args.msd_max_hz is not None:
+            from mask_cyclegan_vc.metrics import ms_bins
+            try:
+                ms_bins(args.msd_n_fft, args.msd_max_hz)
+            except ValueError as exc:
+                self.parser.error("--msd_max_hz: %s" % exc)
         from mask_cyclegan_vc.pitch import check_threshold, lag_range
         try:
             lag_range(args.f0_min, args.f0_max)

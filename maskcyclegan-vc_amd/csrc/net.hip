@@ -26,6 +26,7 @@
 #include "vocoder.h"
 #include "griffinlim.h"
 #include "dtw.h"
+#include "ms.h"
 #include "f0.h"
 #include "../../include/mcvc.h"
 #include <string.h>
@@ -2684,6 +2685,33 @@ int mcvc_f0_stats(const float* fx, long long x_frames, const float* fy, long lon
                   int* counts, float* sums, void* stream)
 {
     return mcvc_f0_stats_launch(fx, x_frames, fy, y_frames, path, pairs, n_pairs, counts, sums, (hipStream_t)stream);
+}
+
+// ---- non-parallel evaluation: modulation spectra, global variance and the distance between two sets (ms_kernels.hip) ----
+int mcvc_ms_max_fft(void) { return MCVC_MS_MAX_FFT; }
+
+int mcvc_ms_launches(void) { return MCVC_MS_LAUNCHES; }
+
+int mcvc_ms_table_init(int n_fft, float* table_host)
+{
+    if (!table_host || ((uintptr_t)table_host & 3)) return MCVC_ERR_INVALID;
+    return mcvc_ms_table_fill(n_fft, table_host);
+}
+
+int mcvc_ms_power(const float* cep, long long n_frames, int K, const int* offs_dev, int n_utts, const int* offs_host, int n_fft, const float* table,
+                  float* power, float* mean, float* var, void* stream)
+{
+    return mcvc_ms_power_launch(cep, n_frames, K, offs_dev, n_utts, offs_host, n_fft, table, power, mean, var, (hipStream_t)stream);
+}
+
+int mcvc_ms_mean_log(const float* values, int n, long long R, float floor, float* out, void* stream)
+{
+    return mcvc_ms_mean_log_launch(values, n, R, floor, out, (hipStream_t)stream);
+}
+
+int mcvc_ms_distance(const float* a, const float* b, int K, int n_bins, int n_used, float* per_dim, float* total, void* stream)
+{
+    return mcvc_ms_distance_launch(a, b, K, n_bins, n_used, per_dim, total, (hipStream_t)stream);
 }
 
 int mcvc_axpy(float* y, const float* x, float alpha, long long n, void* stream)

@@ -125,6 +125,12 @@ _SIGS = {
     "mcvc_f0_launches": (c_int, [c_int]),
     "mcvc_f0_track": (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
     "mcvc_f0_stats": (c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "mcvc_ms_max_fft": (c_int, []),
+    "mcvc_ms_launches": (c_int, []),
+    "mcvc_ms_table_init": (c_int, [c_int, c_void_p]),
+    "mcvc_ms_power": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mcvc_ms_mean_log": (c_int, [c_void_p, c_int, c_longlong, c_float, c_void_p, c_void_p]),
+    "mcvc_ms_distance": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "mcvc_axpy": (c_int, [c_void_p, c_void_p, c_float, c_longlong, c_void_p]),
     "mcvc_conv2d_pack_floats": (c_longlong, [c_int, c_int, c_int, c_int]),
     "mcvc_conv2d_forward": (c_int, [c_void_p] * 6 + [c_int] * 12 + [c_void_p]),

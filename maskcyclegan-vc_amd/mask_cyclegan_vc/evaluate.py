@@ -19,7 +19,14 @@ project, not tables in papers.
 ``--f0`` (needs ``--target_wav_dir``) adds the pitch columns: F0 RMSE and bias in cents and the voiced/unvoiced error along the same DTW
 alignment (mask_cyclegan_vc/pitch.py, metrics.f0_distortion), from the ``<i>-converted_*.wav`` files of ``--converted_audio_dir`` (default
 ``<save_dir>/<name>/converted_audio``, what ``mask_cyclegan_vc.test`` writes with a decoder) and the target recordings.  Without the flag the
-run and its ``metrics.json`` are what they were."""
+run and its ``metrics.json`` are what they were.
+
+``--msd`` adds an ``"msd"`` object: the modulation-spectrum distance and the global-variance distance (dB) of ALL converted utterances
+against ALL utterances of the target speaker (metrics.msd; ``--msd_n_fft``, ``--msd_max_hz``).  The two sets are not index-matched and need
+not be parallel.  ``target_split_half_msd`` scores the target's even-indexed against its odd-indexed utterances: the floor a perfect
+conversion would reach (null with fewer than two).  With ``--source_speaker_id`` the unconverted source gives ``baseline_msd`` /
+``baseline_gvd``.  ``--no_mcd`` (with ``--msd``, not with ``--f0``) serves a corpus without parallel sentences: no MCD, no baseline MCD, no
+index contract; the report then holds ``n_utterances``, per utterance ``index``, ``file`` and ``frames_converted``, and the ``msd`` object."""
 import glob
 import json
 import os
@@ -91,6 +98,34 @@ def _voiced_median(tracks):
     return float(np.median(v)) if v.size else None
 
 
+MSD_UNIT = ("dB; root mean square difference of the two sets' mean log modulation spectra (msd) / mean log global variances (gvd) of mel-cepstra "
+            "from the 80-band log-mel (not WORLD) at 86.13 frames per second (not 200): compares runs of this project, not tables in papers")
+
+
+def msd_report(args, converted, refs, source=None):
+    """The ``"msd"`` object of the report: all converted against all target utterances."""
+    res = metrics.msd(converted, refs, args.n_cep, args.msd_n_fft, args.msd_max_hz)
+    out = {"msd": res["msd"], "gvd": res["gvd"], "msd_per_dim": [float(v) for v in res["msd_per_dim"]],
+           "lgv_converted": [float(v) for v in res["lgv_converted"]], "lgv_target": [float(v) for v in res["lgv_target"]],
+           "n_converted": res["n_converted"], "n_target": res["n_target"], "n_fft": res["n_fft"], "max_hz": res["max_hz"], "floor": res["floor"],
+           "unit": MSD_UNIT, "target_split_half_msd": None}
+    if len(refs) >= 2:
+        out["target_split_half_msd"] = metrics.msd(refs[0::2], refs[1::2], args.n_cep, args.msd_n_fft, args.msd_max_hz)["msd"]
+    if source is not None:
+        base = metrics.msd(source, refs, args.n_cep, args.msd_n_fft, args.msd_max_hz)
+        out.update(baseline_msd=base["msd"], baseline_gvd=base["gvd"])
+    return out
+
+
+def _msd_clause(m):
+    line = "MSD %.3f dB, GVD %.3f dB (%d converted against %d target utterances, n_fft %d" % (m["msd"], m["gvd"], m["n_converted"], m["n_target"], m["n_fft"])
+    if m["target_split_half_msd"] is not None:
+        line += "; target split-half MSD %.3f dB" % m["target_split_half_msd"]
+    if "baseline_msd" in m:
+        line += "; unconverted baseline MSD %.3f dB, GVD %.3f dB" % (m["baseline_msd"], m["baseline_gvd"])
+    return line + ")"
+
+
 def _pick(refs, ids, what):
     for i in ids:
         if i >= len(refs):
@@ -115,11 +150,22 @@ def evaluate(args):
         refs = Audio2Mel().bank(ref_waves)
     else:
         refs = speaker_mels(args.preprocessed_data_dir, args.target_speaker_id)
+    if args.no_mcd:
+        source = _pick(speaker_mels(args.preprocessed_data_dir, args.source_speaker_id), ids, "source utterance") if args.source_speaker_id else None
+        utts = [{"index": i, "file": os.path.basename(p), "frames_converted": int(converted[k].shape[1])} for k, (i, p) in enumerate(files)]
+        report = {"n_cep": int(args.n_cep), "n_utterances": len(utts), "utterances": utts, "msd": msd_report(args, converted, refs, source)}
+        os.makedirs(run_dir, exist_ok=True)
+        out = os.path.join(run_dir, "metrics.json")
+        with open(out, "w") as fh:
+            json.dump(report, fh, indent=2)
+        print(_msd_clause(report["msd"]) + " -> " + out)
+        return report
     target = _pick(refs, ids, "reference")
     res = metrics.mcd(converted, target, args.n_cep)
     base = None
     if args.source_speaker_id:
-        base = metrics.mcd(_pick(speaker_mels(args.preprocessed_data_dir, args.source_speaker_id), ids, "source utterance"), target, args.n_cep)
+        source = _pick(speaker_mels(args.preprocessed_data_dir, args.source_speaker_id), ids, "source utterance")
+        base = metrics.mcd(source, target, args.n_cep)
     utts = []
     for k, (i, p) in enumerate(files):
         u = {"index": i, "file": os.path.basename(p), "mcd": float(res["mcd"][k]), "length": int(res["length"][k]),
@@ -148,6 +194,8 @@ def evaluate(args):
                         "unit": F0_UNIT}
         for key in ("rmse_cents", "bias_cents", "vuv_error"):
             report["f0"][key] = _stats(f0[key][keep]) if keep.any() else None
+    if args.msd:
+        report["msd"] = msd_report(args, converted, refs, source if base is not None else None)
     os.makedirs(run_dir, exist_ok=True)
     out = os.path.join(run_dir, "metrics.json")
     with open(out, "w") as fh:
@@ -160,6 +208,8 @@ def evaluate(args):
             report["f0"]["rmse_cents"]["mean"], report["f0"]["bias_cents"]["mean"], 100.0 * report["f0"]["vuv_error"]["mean"], report["f0"]["n_utterances_voiced"])
     elif args.f0:
         line += " | F0: no utterance with a voiced pair"
+    if args.msd:
+        line += " | " + _msd_clause(report["msd"])
     print(line + " -> " + out)
     return report
 

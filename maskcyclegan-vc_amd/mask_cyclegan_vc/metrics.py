@@ -5,7 +5,9 @@
 * ``mel_cepstra(mels, n_cep=24)``               log10-mels [80, T_i] -> cepstra bank ([n_cep, N], offsets);
 * ``mcd(converted_mels, target_mels, n_cep=24)`` -> per-pair dB, path lengths and the mean;
 * ``f0_stats(f0_x, f0_y, paths)``                F0 tracks + warping paths -> per-pair F0 RMSE / bias in cents and voiced/unvoiced error;
-* ``f0_distortion(conv_wavs, tgt_wavs, conv_mels, tgt_mels, n_cep=24, tracker=None)`` -> the same from waveforms and their log-mels.
+* ``f0_distortion(conv_wavs, tgt_wavs, conv_mels, tgt_mels, n_cep=24, tracker=None)`` -> the same from waveforms and their log-mels;
+* ``modulation_spectrum(feats, n_fft=4096)``     ragged batch -> modulation power [n, K, n_fft/2], mean and global variance [n, K];
+* ``msd(converted_mels, target_mels, n_cep=24, n_fft=4096, max_hz=None)`` -> modulation-spectrum distance and GV distance of two SETS.
 
 Definitions (tests/dtw_checker.py restates them in float64):
 
@@ -34,6 +36,24 @@ F0 statistics (csrc/f0_kernels.hip through ``mcvc_f0_stats``; the tracks come fr
 c = 1200 log2(fx[i] / fy[j]) cents, ``bias_cents`` = mean c, ``rmse_cents`` = sqrt(mean c^2), ``vuv_error`` = (x only + y only) / length.
 A pair without a both-voiced row has ``voiced_pairs`` 0 and ``nan`` for the two cent figures: a documented value, not an exception.
 One wavefront per pair, a fixed reduction order, no atomics: a batch equals its single calls bit for bit.
+
+Modulation spectra and global variance (csrc/ms_kernels.hip through ``mcvc_ms_power``, ``mcvc_ms_mean_log`` and ``mcvc_ms_distance``;
+tests/ms_checker.py restates this in float64).  These need no alignment and no parallel sentences: they compare two *sets* of utterances.
+Input: a cepstra bank [K, N] with offsets as ``mel_cepstra`` returns it, 1 <= K <= 80; utterance u has T frames; ``n_fft`` is 1024, 2048 or
+4096 (the default, = ``max_frames()``), and T <= n_fft: a longer utterance is refused, nothing is truncated.  Per utterance and row k:
+mean[u, k] = (1/T) sum_t c[k, t];  x[t] = c[k, t] - mean[u, k];  var[u, k] = (1/T) sum_t x[t]^2, the population variance from the deviations
+(never E[c^2] - E[c]^2);  X[f] = sum_{t < T} x[t] exp(-2 pi i f t / n_fft) for f = 1 .. n_fft / 2: a rectangular window zero-padded to
+n_fft, bin 0 dropped because the mean was removed;  modulation power P[u, k, f] = |X[f]|^2 / T;  bin f lies at f (22050 / 256) / n_fft Hz.
+Twiddles come from a table of cos(2 pi j / n_fft), j < n_fft, computed in float64 on the host, rounded once and uploaded once per device
+and n_fft; the sine is the same table a quarter turn on; the table is indexed with the *integer* phase (f t) mod n_fft -- exact argument
+reduction, the phase is never formed in floating point.  Per set of n utterances, with floor = 1e-10 (a definition, not a tolerance):
+LMS[k, f] = (1/n) sum_u 10 log10(max(P[u, k, f], floor)) and LGV[k] = (1/n) sum_u 10 log10(max(var[u, k], floor)), in dB, utterances
+summed in index order.  Between two sets A and B, which may differ in size and need not be parallel, over the F bins at or below
+``max_hz`` (default: all n_fft / 2 bins, up to Nyquist = 43.07 Hz):  msd_per_dim[k] = sqrt((1/F) sum_f (LMS_A - LMS_B)^2),
+msd = sqrt((1/(K F)) sum_{k, f} (LMS_A - LMS_B)^2),  gvd = sqrt((1/K) sum_k (LGV_A - LGV_B)^2), all in dB.  No atomics, every reduction in a
+fixed order; an utterance's P, mean and var depend on that utterance alone, so a ragged batch equals its single calls bit for bit.  One
+``msd()`` is 2 + 4 + 2 = ``mcvc_ms_launches()`` = 8 launches after the two cepstra projections.  Comparability: as for MCD the cepstra
+come from the 80-band log-mel, not from WORLD, at 86.13 frames per second, not 200: the numbers compare runs of this project.
 """
 import ctypes
 import math
@@ -47,6 +67,9 @@ N_MEL = 80
 MAX_K = 80
 TABLE_COLS = 6
 MCD_SCALE = (10.0 / math.log(10.0)) * math.sqrt(2.0)
+MS_FFTS = (1024, 2048, 4096)
+MS_FLOOR = 1e-10
+FRAME_RATE = 22050.0 / 256.0
 
 
 def dct_basis(n_cep):
@@ -265,3 +288,115 @@ def f0_distortion(conv_wavs, tgt_wavs, conv_mels, tgt_mels, n_cep=24, tracker=No
     res = f0_stats(fx, fy, paths)
     res.update(f0_converted=fx, f0_target=fy, lags=tracker.lags, threshold=tracker.threshold)
     return res
+
+
+def host_ms_table(n_fft):
+    """cos(2 pi j / n_fft), j < n_fft, as a float32 host array (``mcvc_ms_table_init``)."""
+    n_fft = _check_fft(n_fft)
+    host = np.empty(n_fft, dtype=np.float32)
+    _hip.check(_hip.lib().mcvc_ms_table_init(n_fft, host.ctypes.data), "mcvc_ms_table_init")
+    return host
+
+
+def _check_fft(n_fft):
+    if isinstance(n_fft, bool) or int(n_fft) != n_fft or int(n_fft) not in MS_FFTS:
+        raise ValueError("n_fft must be one of %s, got %r" % (", ".join(map(str, MS_FFTS)), n_fft))
+    return int(n_fft)
+
+
+def ms_bins(n_fft, max_hz=None):
+    """-> (F, max_hz): the number of leading bins f = 1 .. F at or below ``max_hz`` (None: all n_fft / 2, up to Nyquist)."""
+    n_fft = _check_fft(n_fft)
+    nyquist = FRAME_RATE / 2.0
+    if max_hz is None:
+        return n_fft // 2, nyquist
+    max_hz = float(max_hz)
+    if not math.isfinite(max_hz) or max_hz > nyquist:
+        raise ValueError("max_hz must not lie above Nyquist, %.2f Hz at %.2f frames per second, got %r" % (nyquist, FRAME_RATE, max_hz))
+    F = int(math.floor(max_hz * n_fft / FRAME_RATE + 1e-9))
+    if F < 1:
+        raise ValueError("max_hz %r selects no bin: the first bin of n_fft %d lies at %.4f Hz" % (max_hz, n_fft, FRAME_RATE / n_fft))
+    return min(F, n_fft // 2), max_hz
+
+
+def modulation_spectrum(feats, n_fft=4096):
+    """Ragged batch (list of [K, T_i], or ``(bank, offs)``) -> dict of device tensors ``power`` [n, K, n_fft / 2] (bin f at index f - 1),
+    ``mean`` [n, K], ``var`` [n, K], plus ``offs`` and ``n_fft``; one launch on the current stream.  ``power`` takes 4 n K n_fft / 2 bytes:
+    6.9 MB for 35 utterances at K = 24 and n_fft = 4096.  ValueError: an n_fft outside 1024 / 2048 / 4096, an utterance longer than n_fft,
+    a bank that is not on the device, features that are not finite."""
+    n_fft = _check_fft(n_fft)
+    if isinstance(feats, tuple) and len(feats) == 2 and isinstance(feats[0], torch.Tensor) and not feats[0].is_cuda:
+        raise ValueError("the bank of a (bank, offs) pair must live on a HIP device; there is no CPU path")
+    b, offs = bank(feats)
+    lens = np.diff(offs)
+    if int(lens.max()) > n_fft:
+        u = int(np.argmax(lens > n_fft))
+        raise ValueError("utterance %d has %d frames, more than n_fft = %d: nothing is truncated" % (u, int(lens[u]), n_fft))
+    dev, K, n = b.device, b.shape[0], len(lens)
+    table = _hip.device_constant(("metrics.ms_table", n_fft), dev, lambda: host_ms_table(n_fft))
+    with torch.no_grad(), torch.cuda.device(dev):
+        offs_d = torch.from_numpy(offs).to(dev)
+        power = torch.empty(n, K, n_fft // 2, dtype=torch.float32, device=dev)
+        mean = torch.empty(n, K, dtype=torch.float32, device=dev)
+        var = torch.empty(n, K, dtype=torch.float32, device=dev)
+        _hip.check(_hip.lib().mcvc_ms_power(_hip.ptr(b), b.shape[1], K, _hip.ptr(offs_d), n, offs.ctypes.data, n_fft, _hip.ptr(table), _hip.ptr(power),
+                                            _hip.ptr(mean), _hip.ptr(var), _hip.stream()), "mcvc_ms_power")
+    return {"power": power, "mean": mean, "var": var, "offs": offs, "n_fft": n_fft}
+
+
+def mean_log(values, floor=MS_FLOOR):
+    """device [n, ...] -> device [...]: (1/n) sum_u 10 log10(max(values[u], floor)) in dB, utterances in index order; one launch."""
+    floor = float(floor)
+    if not (floor > 0.0 and math.isfinite(floor)):
+        raise ValueError("floor must be positive and finite, got %r" % (floor,))
+    dev = _hip.hip_device("mask_cyclegan_vc.metrics", values.device if isinstance(values, torch.Tensor) and values.is_cuda else None)
+    _hip.require_on_device("mask_cyclegan_vc.metrics", values, dev, "values", "metrics")
+    if values.dim() < 2 or values.shape[0] < 1 or values[0].numel() < 1:
+        raise ValueError("expected [n, ...] values with n >= 1, got %s" % (tuple(values.shape),))
+    v = values.detach().to(torch.float32).contiguous()
+    with torch.no_grad(), torch.cuda.device(dev):
+        out = torch.empty(v.shape[1:], dtype=torch.float32, device=dev)
+        _hip.check(_hip.lib().mcvc_ms_mean_log(_hip.ptr(v), v.shape[0], out.numel(), floor, _hip.ptr(out), _hip.stream()), "mcvc_ms_mean_log")
+    return out
+
+
+def table_distance(a, b, n_used=None):
+    """device tables [K, n_bins] (or [K]: one row of K bins) -> (per_dim [rows], total [1]) device tensors: the root mean square of a - b
+    over the first ``n_used`` bins of every row and over all of them; one launch, one workgroup."""
+    dev = _hip.hip_device("mask_cyclegan_vc.metrics", a.device if isinstance(a, torch.Tensor) and a.is_cuda else None)
+    _hip.require_on_device("mask_cyclegan_vc.metrics", a, dev, "a", "metrics")
+    _hip.require_on_device("mask_cyclegan_vc.metrics", b, dev, "b", "metrics")
+    if a.shape != b.shape or a.dim() not in (1, 2):
+        raise ValueError("expected two tables of one shape [K, n_bins] or [K], got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    a2 = a.detach().to(torch.float32).contiguous().reshape(1 if a.dim() == 1 else a.shape[0], -1)
+    b2 = b.detach().to(torch.float32).contiguous().reshape(a2.shape)
+    rows, n_bins = a2.shape
+    n_used = n_bins if n_used is None else int(n_used)
+    if not 1 <= rows <= MAX_K or not 1 <= n_bins <= MS_FFTS[-1] // 2 or not 1 <= n_used <= n_bins:
+        raise ValueError("tables of 1 .. %d rows and 1 .. %d bins, 1 <= n_used <= n_bins; got %s, n_used %d" % (MAX_K, MS_FFTS[-1] // 2, tuple(a2.shape), n_used))
+    with torch.no_grad(), torch.cuda.device(dev):
+        per_dim = torch.empty(rows, dtype=torch.float32, device=dev)
+        total = torch.empty(1, dtype=torch.float32, device=dev)
+        _hip.check(_hip.lib().mcvc_ms_distance(_hip.ptr(a2), _hip.ptr(b2), rows, n_bins, n_used, _hip.ptr(per_dim), _hip.ptr(total), _hip.stream()),
+                   "mcvc_ms_distance")
+    return per_dim, total
+
+
+def msd(converted_mels, target_mels, n_cep=24, n_fft=4096, max_hz=None):
+    """Modulation-spectrum distance and global-variance distance (dB) between two SETS of log10-mels, which may differ in size and need not
+    be parallel: cepstra, ``modulation_spectrum`` of both sets, the mean-log tables, the distances -- ``mcvc_ms_launches()`` = 8 launches after
+    the two projections.  -> dict: ``msd``, ``gvd`` (floats), ``msd_per_dim`` [n_cep], ``lgv_converted`` / ``lgv_target`` [n_cep],
+    ``lms_converted`` / ``lms_target`` [n_cep, n_fft / 2] (numpy), ``n_converted``, ``n_target``, ``n_fft``, ``n_bins_used``, ``max_hz``,
+    ``floor``.  Each set's ``power`` array takes 4 n n_cep n_fft / 2 bytes on the device: 6.9 MB for 35 utterances at the defaults.
+    ValueError: an utterance longer than n_fft, an n_fft outside 1024 / 2048 / 4096, a max_hz that selects no bin or lies above Nyquist."""
+    F, hz = ms_bins(n_fft, max_hz)
+    sides = []
+    for mels in (converted_mels, target_mels):
+        ms = modulation_spectrum(mel_cepstra(mels, n_cep), n_fft)
+        sides.append((mean_log(ms["power"]), mean_log(ms["var"]), ms["power"].shape[0]))
+    (lms_x, lgv_x, nx), (lms_y, lgv_y, ny) = sides
+    per_dim, total = table_distance(lms_x, lms_y, F)
+    _, gv = table_distance(lgv_x, lgv_y)
+    return {"msd": float(total.cpu()[0]), "gvd": float(gv.cpu()[0]), "msd_per_dim": per_dim.cpu().numpy(),
+            "lgv_converted": lgv_x.cpu().numpy(), "lgv_target": lgv_y.cpu().numpy(), "lms_converted": lms_x.cpu().numpy(), "lms_target": lms_y.cpu().numpy(),
+            "n_converted": int(nx), "n_target": int(ny), "n_fft": int(n_fft), "n_bins_used": int(F), "max_hz": float(hz), "floor": MS_FLOOR}
