@@ -281,6 +281,21 @@ int mcvc_gen_update_ranges(const float* const* params, const long long* numel, f
 int mcvc_disc_update_batch(const float* const* params, const long long* numel, float* packed, int max_batch, int T,
                            const float* flat, float* grad, float* grad2, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                            float beta2, float eps, int step, float grad_scale, int zero_grads, void* stream);
+
+/* Host view of the job table a re-pack or fused update would use (pure host code, no device call): what mcvc_gen_pack_ranges (net 0) /
+ * mcvc_disc_pack_batch (net 1; sets = 3, range_mask = 7) or, with update = 1, mcvc_gen_update_ranges / mcvc_disc_update_batch builds for
+ * these arguments, as rows of 20 64-bit integers whose first entry names the record:
+ *   0  header: net, update, jobs, owners, dgrad-argument entries, workgroups, packed floats, traced bytes and written bytes (bit patterns of
+ *      the doubles), the planner's flags (generator: fused | wino_only<<1 | w4<<2 | w43<<3 | up1_w4<<4 | up1_w2<<5 | up2_w2<<6;
+ *      discriminator: 1 full table, 4 implicit-GEMM table), 20
+ *   1  job, in table order: layer index, form, kind, param, dst, floats of the region [dst, dst + len) it writes into, block0, gx, Cout, Cin,
+ *      K, ld, co_off, KW, taps, xi_stride, dg
+ *   2  owner (update = 1): param, block0, gx, Cout, Cin, taps, CB, IB, e0, ne, flat, vec4
+ *   3  per layer the call touches: layer index, sets, the mask of forms it leaves fresh there
+ *   4  dgrad arguments: index, Cin, KH, KW, step, ld, co_off, merged, mg_kh, mg_kw, ncls, tapmajor, cout_rows
+ *   5  one of their classes: index, class, nth, ntw, khmax, kwmax, pad_h, pad_w, qh, qw, su, sv, offset
+ * *n_rows = rows of the plan; MCVC_ERR_WORKSPACE when cap is smaller (the first cap rows are written), MCVC_ERR_INVALID as the entries. */
+int mcvc_pack_plan(int net, int max_batch, int T, int sets, int range_mask, int update, long long* rows, int cap, int* n_rows);
 int mcvc_axpy(float* y, const float* x, float alpha, long long n, void* stream);
 
 /* ---- on-device input pipeline: replaces VCDataset.__getitem__ + DataLoader collate + 4 H2D copies per iteration

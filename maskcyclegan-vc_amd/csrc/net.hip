@@ -16,6 +16,7 @@
 #include "mcvc_common.h"
 #include "twin.h"
 #include "pack.h"
+#include "packforms.h"
 #include "misc.h"
 #include "trunk.h"
 #include "wino.h"
@@ -31,6 +32,8 @@
 #include "../../include/mcvc.h"
 #include <string.h>
 #include <algorithm>
+#include <array>
+#include <tuple>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -45,6 +48,9 @@ constexpr float kInEps = 1e-5f;
 struct View { float* p; long long sb, sc; int sh; };
 struct CView { const float* p; long long sb, sc; int sh; };
 static inline CView cv(const View& v) { return CView{v.p, v.sb, v.sc, v.sh}; }
+
+constexpr int kMaxLayers = 20;
+struct PackFresh { unsigned layer[kMaxLayers]; PackFresh() { for (unsigned& m : layer) m = kAllForms; } };
 
 struct Exec {
     hipStream_t s;
@@ -78,23 +84,23 @@ struct Exec {
     int wgrad_x_xs = 0;            // conv_wgrad: x is in the phase-split padded layout
     int force_scheme = 0;          // op-level entries (mcvc_layer_*): 0 planner's choice, 1 Winograd with 2x2 output tiles only, 2 with 4x4 tiles
                                    // (thresholds on samples / tiles lifted), 3 no Winograd, 4 no Winograd and no staged GEMM (direct kernels)
-    int pack_skips;                // what the last re-pack of `packed` left stale: bit 0 = generic trunk copies, bit 1 = direct copies of the Winograd layers
+    PackFresh fresh;               // per layer, the forms the last re-pack of `packed` left fresh (never packed through a restricted entry: all)
     unsigned* sync;                // arrival counters of the persistent trunk kernels (MCVC_TRUNK_SYNC_WORDS words of the scratch)
     std::vector<std::pair<const void*, hipEvent_t>> readers;
     void fail(int e) { if (!err && e) err = e; }
 };
 
-// What the last re-pack of a packed-weight buffer skipped (mcvc_gen_pack_small_batch refreshes only the copies the small-batch schedule
-// reads).  The run-time dispatch predicates and the pack predicate are written separately; if they ever diverge, the generic path would
-// read zero / stale weights silently -- so every pass looks its buffer up and the generic paths refuse to run on a skipped region.
+// What the last re-pack of a packed-weight buffer left fresh: per layer (ConvSpec::index) the mask of forms it refreshed.  The restricted
+// entries (mcvc_gen_pack_ranges, the fused updates, mcvc_disc_pack_batch) refresh only the forms their schedule reads; each records the
+// very masks it built its job table from (record_fresh), every pass looks its buffer up, and a kernel about to read a form that is not
+// fresh fails the pass (stale) or takes the scheme whose sets are (wino4_applies / wino43_applies) instead of reading old weights.
 static std::mutex g_pack_mu;
-static std::map<const void*, int> g_pack_skips;
-static void set_pack_skips(const void* packed, int skips) { std::lock_guard<std::mutex> lk(g_pack_mu); g_pack_skips[packed] = skips; }
-static int get_pack_skips(const void* packed)
+static std::map<const void*, PackFresh> g_pack_fresh;
+static PackFresh get_fresh(const void* packed)
 {
     std::lock_guard<std::mutex> lk(g_pack_mu);
-    auto it = g_pack_skips.find(packed);
-    return it == g_pack_skips.end() ? 0 : it->second;          // never packed through the small-batch entry: assume a full pack
+    auto it = g_pack_fresh.find(packed);
+    return it == g_pack_fresh.end() ? PackFresh() : it->second;          // never seen: assume a full pack
 }
 
 // small pool of timing-less events, reused round-robin (a backward pass uses a few dozen; the pool is far larger, so an
@@ -111,6 +117,17 @@ static hipEvent_t pool_event()
     }
     next = (next + 1) % pool.size();
     return pool[next];
+}
+
+static bool is_fresh(const Exec& ex, const ConvSpec& c, PackForm f) { return (ex.fresh.layer[c.index] >> f & 1) != 0; }
+// (a weight gradient reads no weight set; it follows the scheme of the buffer's schedule: the one some layer's fresh sets stand for)
+static bool any_fresh(const Exec& ex, PackForm f) { for (unsigned m : ex.fresh.layer) if (m >> f & 1) return true; return false; }
+// a kernel is about to read form f of layer c: fail the pass when the last re-pack did not refresh it
+static bool stale(Exec& ex, const ConvSpec& c, PackForm f)
+{
+    if (ex.dry || is_fresh(ex, c, f)) return false;
+    ex.fail(MCVC_ERR_INVALID);
+    return true;
 }
 
 // the main stream is about to overwrite `buf`: wait for aux-stream kernels that still read it
@@ -133,128 +150,6 @@ static void join_aux(Exec& ex)
 }
 
 // -------------------------------------------------------------------------------------------------
-struct ConvSpec {
-    int Cin, Cout, nbr, KH, KW, stride, ph, pw;
-    int wi[2], bi[2];
-    int has_bias_grad;
-    // derived
-    int cout_tot, cout_pk, cin_pad, w_rows, cin_pk, dg_rows_co;
-    long long off_fwd, off_bias, off_dgrad;
-    // 5x5 stride-1 single-branch convs (upSample1/2): Winograd F(2x2,5x5) weight sets U[36][K+1][ld], forward and data-gradient
-    int wino; long long off_wf, off_wd, wf_xi, wd_xi;
-    long long off_w4f, off_w4d;    // ... and their F(4x4,5x5) twins U[64][...] (wino4.h; same row / column conventions and strides per point)
-    // 5x5 stride-2 convs (downSample1/2): their merged 3x3 data-gradient as Winograd F(2x2,3x3): U[16][co (+1)][mg_ld]
-    int wino3; long long off_w3, w3_xi;
-    long long off_w3f, w3f_xi;     // forward twin over the four input phases: U[16][4*Cin (+1)][cout_pk]
-    long long off_w43, off_w43f;   // ... and the 36-point F(4x4,3x3) sets of both (wino43_kernels.hip), same strides per point
-    long long off_tk;          // KH == 1 convs: transposed + flipped [Cin][cout_tot*KW] copy for the fused small-batch trunk dgrad
-    int ncls;
-    DgradClass cls[4];
-    // stride 2: the four output-parity classes are ONE stride-1 conv with 4*Cin output channels (4*ci + 2*qh + qw) whose
-    // taps are zero-padded to a common window; its PixelShuffle(2) store scatters straight into dX[ci][2a+qh][2b+qw]
-    int merged, mg_kh, mg_kw, mg_pad_h, mg_pad_w, mg_ld;
-    // 3x3 stride-2 convs (the discriminators') at large batch: the merged matrix multiplies 16 tap slots of which 9 are non-zero; with
-    // enough pixels to fill the chip per launch the four parity classes run as four exact stride-1 convs instead (1.78x fewer MACs)
-    long long off_dcls;            // -1: no per-class copies
-    DgradClass ucls[4];
-    // 3x3 stride-2 padding-1 layers (the discriminators'): implicit-GEMM operands (sgemm.h) -- the forward copy with tap-major rows and the
-    // four parity classes' data-gradient matrices with rows (tap, co)
-    int igemm; long long off_ifwd, off_idg; DgradClass icls[4];
-};
-
-static void spec_finalize(ConvSpec& c, long long& cur)
-{
-    c.cout_tot = c.Cout * c.nbr;
-    c.cout_pk = round_up_i(c.cout_tot, 32);
-    c.cin_pad = round_up_i(c.Cin, 2);
-    c.w_rows = c.cin_pad * c.KH * c.KW;
-    c.off_fwd = cur; cur += (long long)(c.w_rows + 1) * c.cout_pk;      // + one all-zero pad row (DMA target for k >= K)
-    c.off_bias = cur; cur += c.cout_pk;
-    c.cin_pk = round_up_i(c.Cin, 32);
-    c.dg_rows_co = round_up_i(c.cout_tot, 2);
-    c.off_dgrad = cur;
-    c.ncls = 0;
-    const int st = c.stride;
-    for (int qh = 0; qh < st; ++qh) {
-        for (int qw = 0; qw < st; ++qw) {
-            DgradClass k{};
-            const int khmin = (qh + c.ph) % st, kwmin = (qw + c.pw) % st;
-            if (khmin > c.KH - 1 || kwmin > c.KW - 1) continue;
-            k.khmax = khmin + st * ((c.KH - 1 - khmin) / st);
-            k.kwmax = kwmin + st * ((c.KW - 1 - kwmin) / st);
-            k.nth = (k.khmax - khmin) / st + 1;
-            k.ntw = (k.kwmax - kwmin) / st + 1;
-            k.pad_h = (k.khmax - qh - c.ph) / st;
-            k.pad_w = (k.kwmax - qw - c.pw) / st;
-            k.qh = qh; k.qw = qw;
-            k.offset = cur - c.off_dgrad;
-            if (st == 1) cur += ((long long)c.dg_rows_co * k.nth * k.ntw + 1) * c.cin_pk;   // + zero pad row
-            c.cls[c.ncls++] = k;
-        }
-    }
-    c.merged = 0;
-    if (st == 2) {
-        c.merged = 1;
-        c.mg_pad_h = c.mg_pad_w = 0;
-        for (int k = 0; k < c.ncls; ++k) {
-            if (c.cls[k].pad_h > c.mg_pad_h) c.mg_pad_h = c.cls[k].pad_h;
-            if (c.cls[k].pad_w > c.mg_pad_w) c.mg_pad_w = c.cls[k].pad_w;
-        }
-        c.mg_kh = c.mg_kw = 1;
-        for (int k = 0; k < c.ncls; ++k) {
-            DgradClass& d = c.cls[k];
-            d.su = c.mg_pad_h - d.pad_h; d.sv = c.mg_pad_w - d.pad_w; d.offset = 0;
-            if (d.su + d.nth > c.mg_kh) c.mg_kh = d.su + d.nth;
-            if (d.sv + d.ntw > c.mg_kw) c.mg_kw = d.sv + d.ntw;
-        }
-        c.mg_ld = round_up_i(4 * c.Cin, 32);
-        cur += ((long long)c.dg_rows_co * c.mg_kh * c.mg_kw + 1) * c.mg_ld;                  // + zero pad row
-    }
-    c.off_dcls = -1;
-    if (st == 2 && c.KH == 3 && c.KW == 3 && c.Cin >= 64) {
-        cur = (cur + 3) & ~3LL;
-        c.off_dcls = cur;
-        for (int k = 0; k < c.ncls; ++k) {
-            c.ucls[k] = c.cls[k];
-            c.ucls[k].offset = cur - c.off_dcls;
-            cur += ((long long)c.dg_rows_co * c.cls[k].nth * c.cls[k].ntw + 1) * c.cin_pk;   // + zero pad row
-        }
-    }
-    c.igemm = 0; c.off_ifwd = c.off_idg = -1;
-    if (st == 2 && c.KH == 3 && c.KW == 3 && c.ph == 1 && c.pw == 1 && (c.Cin % 64) == 0 && (c.cout_tot % 64) == 0 && c.ncls == 4) {
-        c.igemm = 1;
-        cur = (cur + 3) & ~3LL;
-        c.off_ifwd = cur; cur += (long long)9 * c.Cin * c.cout_pk;
-        // (the implicit data gradient reads this tap-major forward copy row-major -- sgemm.h arow -- its per-class copies of r4 are gone)
-        for (int k = 0; k < c.ncls; ++k) { c.icls[k] = c.cls[k]; c.icls[k].offset = 0; }
-    }
-    cur = (cur + 3) & ~3LL;
-    c.wino = (c.KH == 5 && c.KW == 5 && st == 1 && c.nbr == 1 && c.Cin >= 64 && c.Cout >= 64) ? 1 : 0;
-    c.off_wf = c.off_wd = c.off_w4f = c.off_w4d = -1; c.wf_xi = c.wd_xi = 0;
-    if (c.wino) {
-        c.wf_xi = (long long)(c.cin_pad + 1) * c.cout_pk;                          // rows ci (+ zero pad row), columns co
-        c.off_wf = cur; cur += 36 * c.wf_xi;
-        c.wd_xi = (long long)(c.dg_rows_co + 1) * c.cin_pk;                       // rows co, columns ci
-        c.off_wd = cur; cur += 36 * c.wd_xi;
-        cur = (cur + 3) & ~3LL;
-        c.off_w4f = cur; cur += 64 * c.wf_xi;
-        c.off_w4d = cur; cur += 64 * c.wd_xi;
-        cur = (cur + 3) & ~3LL;
-    }
-    c.wino3 = (c.merged && c.KH == 5 && c.KW == 5 && c.ph == 2 && c.pw == 2 && (4 * c.Cin) % 128 == 0 && c.cout_tot % 16 == 0) ? 1 : 0;
-    c.off_w3 = -1; c.w3_xi = 0;
-    c.off_w3f = -1; c.w3f_xi = 0;
-    c.off_w43 = c.off_w43f = -1;
-    if (c.wino3) {
-        c.w3_xi = (long long)(c.dg_rows_co + 1) * c.mg_ld; c.off_w3 = cur; cur += 16 * c.w3_xi; cur = (cur + 3) & ~3LL;
-        c.w3f_xi = (long long)(4 * c.Cin + 1) * c.cout_pk; c.off_w3f = cur; cur += 16 * c.w3f_xi; cur = (cur + 3) & ~3LL;
-        c.off_w43 = cur; cur += 36 * c.w3_xi; cur = (cur + 3) & ~3LL;
-        c.off_w43f = cur; cur += 36 * c.w3f_xi; cur = (cur + 3) & ~3LL;
-    }
-    c.off_tk = -1;
-    if (c.KH == 1 && st == 1) { c.off_tk = cur; cur += (long long)c.Cin * c.cout_tot * c.KW; cur = (cur + 3) & ~3LL; }
-}
-
 static ConvSpec mk(int Cin, int Cout, int nbr, int KH, int KW, int stride, int ph, int pw, int w0, int b0, int w1, int b1, int bias_grad)
 {
     ConvSpec c{};
@@ -329,7 +224,7 @@ static long long wino_chunk_tiles(int NB, long long tiles_per_sample)          /
 // direct-conv kernel as a 1x1 conv over 36 images with per-image weights) -> output transform (+bias, PixelShuffle store).
 // dgrad: the same on the flipped / transposed weight set; K = conv output channels, M = conv input channels.
 // F(4x4,5x5) (wino4.h) from `MCVC_WINO4_NB` samples per pass on images whose sides are multiples of 4, when the packed buffer holds the
-// 64-point weight sets (pack_skips bit 16 clear): 2.25x fewer multiplies and 2.25x smaller V / M than F(2x2,5x5).  Measured (ms/step, off vs on):
+// 64-point weight sets, fresh: 2.25x fewer multiplies and 2.25x smaller V / M than F(2x2,5x5).  Measured (ms/step, off vs on):
 // bs=1 6.77 / 6.64 (upSample2 only: upSample1 has 20 tiles per sample), bs=2 10.8 / 10.3, bs=4 17.5 / 15.1, bs=8 31.1 / 24.3, bs=32 118.1 / 84.5
 // (the last three with F(4x4,3x3) on downSample1/2 as well, MCVC_WINO43_NB: at one sample per pass that one costs 0.3 ms)
 static int wino4_min_nb()
@@ -348,18 +243,20 @@ static int wino43_min_nb()
     static const int nb = mcvc_knob("MCVC_WINO43_NB", 4);
     return nb;
 }
-static bool wino4_applies(const Exec& ex, const ConvSpec& c, int NB, int H, int W)
+static bool wino4_applies(const Exec& ex, const ConvSpec& c, int NB, int H, int W, bool reads_set = true)
 {
     if (ex.force_scheme == 1 || ex.force_scheme >= 3) return false;
-    if (ex.force_scheme == 2) return c.wino && c.off_w4f >= 0 && (H & 3) == 0 && (W & 3) == 0;
-    return c.wino && c.off_w4f >= 0 && wino4_min_nb() > 0 && NB >= wino4_min_nb() && (H & 3) == 0 && (W & 3) == 0 && !(ex.pack_skips & 16);
+    if (ex.force_scheme == 2) return c.wino && (H & 3) == 0 && (W & 3) == 0;
+    return c.wino && wino4_min_nb() > 0 && NB >= wino4_min_nb() && (H & 3) == 0 && (W & 3) == 0 &&
+           (reads_set ? is_fresh(ex, c, PF_W4F) : any_fresh(ex, PF_W4F));
 }
 // F(4x4,3x3) for the stride-2 5x5 layers in phase form (wino43_kernels.hip) under the same conditions (OH x OW = the conv's output size)
-static bool wino43_applies(const Exec& ex, const ConvSpec& c, int NB, int OH, int OW)
+static bool wino43_applies(const Exec& ex, const ConvSpec& c, int NB, int OH, int OW, bool reads_set = true)
 {
     if (ex.force_scheme == 1 || ex.force_scheme >= 3) return false;
-    if (ex.force_scheme == 2) return c.wino3 && c.off_w43 >= 0 && (OH & 3) == 0 && (OW & 3) == 0;
-    return c.wino3 && c.off_w43 >= 0 && wino43_min_nb() > 0 && NB >= wino43_min_nb() && (OH & 3) == 0 && (OW & 3) == 0 && !(ex.pack_skips & 32);
+    if (ex.force_scheme == 2) return c.wino3 && (OH & 3) == 0 && (OW & 3) == 0;
+    return c.wino3 && wino43_min_nb() > 0 && NB >= wino43_min_nb() && (OH & 3) == 0 && (OW & 3) == 0 &&
+           (reads_set ? is_fresh(ex, c, PF_W43F) : any_fresh(ex, PF_W43F));
 }
 // samples per F(4x4) pass: V / M hold pts * max(K, M) * tiles floats
 static int wino4_chunk(const Exec& ex, int NB, long long tiles_per_sample, int KM, int pts)
@@ -515,10 +412,9 @@ static bool conv_wino(Exec& ex, const ConvSpec& c, const float* packed, int dgra
     int nbc = 0;
     if (wino4_applies(ex, c, NB, H, W) && (M % 128) == 0 && (K % 16) == 0) nbc = wino_nbc(ex, *f, NB, wino_tiles(*f, H, W), K > M ? K : M, wino4_min_tiles());
     if (!nbc) {
-        // (bits 128 / 256: the 36-point sets of upSample1 / upSample2 were not refreshed -- gen_pack_cfg skips them for a layer whose EVERY pass at
-        //  the engine's frame count takes the 4 x 4 scheme; recorded per LAYER, so a pass at another frame count on the same packed buffer that
-        //  does reach this path reads no stale set: ADVICE r5)
-        if (!ex.dry && (ex.pack_skips & (c.Cout == 1024 ? 128 : 256))) { ex.fail(MCVC_ERR_INVALID); return true; }
+        // (gen_pack_cfg skips the 36-point sets of a layer whose EVERY pass at the engine's frame count takes the 4 x 4 scheme; a pass at another
+        //  frame count on the same packed buffer that does reach this path reads no stale set: ADVICE r5)
+        if (stale(ex, c, wino_form(false, dgrad))) return true;
         f = &kWino[kF25];
         nbc = wino_nbc(ex, *f, NB, wino_tiles(*f, H, W), K > M ? K : M, 0);
     }
@@ -527,9 +423,9 @@ static bool conv_wino(Exec& ex, const ConvSpec& c, const float* packed, int dgra
     const bool four = f->tile == 4;
     WinoPass p{};
     p.f = f; p.K = K; p.M = M; p.NB = NB; p.nbc = nbc; p.H = H; p.W = W;
-    p.a = packed + (dgrad ? (four ? c.off_w4d : c.off_wd) : (four ? c.off_w4f : c.off_wf));
-    p.a_xi = dgrad ? c.wd_xi : c.wf_xi; p.lda = dgrad ? c.cin_pk : c.cout_pk; p.a_rows = dgrad ? c.dg_rows_co : c.cin_pad;
-    p.bias = dgrad ? nullptr : packed + c.off_bias;
+    const PackForm form = wino_form(four, dgrad);
+    p.a = packed + c.off[form]; p.a_xi = form_xi(c, form); p.lda = kPackForms[form].ld(c); p.a_rows = dgrad ? c.dg_rows_co : c.cin_pad;
+    p.bias = dgrad ? nullptr : packed + c.off[PF_BIAS];
     p.shuffle = shuffle; p.YH = 2 * H; p.YW = 2 * W; p.accumulate = accumulate;
     p.may_defer = !dgrad && shuffle;
     wino_pass(ex, p, x, y);
@@ -560,13 +456,13 @@ static bool conv_wino3(Exec& ex, const ConvSpec& c, const float* packed, int dgr
     const bool four = f->tile == 4;
     WinoPass p{};
     p.f = f; p.K = K; p.M = M; p.NB = NB; p.nbc = nbc; p.H = OH; p.W = OW;
+    const PackForm form = wino3_form(four, dgrad);
+    p.a = packed + c.off[form]; p.a_xi = form_xi(c, form); p.lda = kPackForms[form].ld(c);
     if (dgrad) {
-        p.a = packed + (four ? c.off_w43 : c.off_w3); p.a_xi = c.w3_xi; p.lda = c.mg_ld;
         p.shuffle = 1; p.YH = H; p.YW = W; p.accumulate = accumulate;
     } else {
         p.XH = H; p.XW = W;
-        p.a = packed + (four ? c.off_w43f : c.off_w3f); p.a_xi = c.w3f_xi; p.lda = c.cout_pk;
-        p.bias = packed + c.off_bias;
+        p.bias = packed + c.off[PF_BIAS];
         p.YH = OH; p.YW = OW;
         p.may_defer = true;
     }
@@ -651,13 +547,13 @@ static void conv_fwd_igemm(Exec& ex, const ConvSpec& c, const float* packed, int
     const long long plane = mcvc_xs_plane(H, W);
     IGemmArgs g{};
     g.ncls = 1;
-    g.cls[0].a = packed + c.off_ifwd; g.cls[0].ntaps = 9; g.cls[0].coff = 0;
+    g.cls[0].a = packed + c.off[PF_IFWD]; g.cls[0].ntaps = 9; g.cls[0].coff = 0;
     xs_tap_offsets(H, W, g.cls[0].boff);
     for (int t = 0; t < 9; ++t) g.cls[0].aoff[t] = (long long)t * c.Cin * c.cout_pk;      // tap-major copy: rows (tap, ci)
     g.a_ks = c.cout_pk;
     g.b = xs; g.b_cs = 4 * plane; g.b_sn = (long long)c.Cin * 4 * plane; g.b_pitch = pw; g.Cb = c.Cin; g.OW = OW; g.P = P;
     g.c = y.p; g.ldc = y.sc; g.c_sn = y.sb; g.c_sh = y.sh; g.c_sw = 1;
-    g.bias = packed + c.off_bias;
+    g.bias = packed + c.off[PF_BIAS];
     g.M = c.cout_tot; g.N = (int)NT; g.nsplit = sp; g.c_slab = ex.slabs; g.c_split = y_total;
     ex.fail(mcvc_igemm_launch(g, ex.s));
 }
@@ -684,7 +580,7 @@ static void conv_dgrad_igemm(Exec& ex, const ConvSpec& c, const float* packed, i
     for (int k = 0; k < c.ncls; ++k) {
         const DgradClass& d = c.icls[k];
         IGemmClass& q = g.cls[k];
-        q.a = packed + c.off_ifwd; q.ntaps = d.nth * d.ntw;          // the tap-major FORWARD copy, read row-major (sgemm.h arow)
+        q.a = packed + c.off[PF_IFWD]; q.ntaps = d.nth * d.ntw;          // the tap-major FORWARD copy, read row-major (sgemm.h arow)
         q.coff = (long long)d.qh * dx.sh + d.qw;
         for (int u = 0; u < d.nth; ++u)
             for (int v = 0; v < d.ntw; ++v) {     // input row 2a + qh receives tap kh from output row a + (qh + 1 - kh) / 2
@@ -700,14 +596,6 @@ static void conv_dgrad_igemm(Exec& ex, const ConvSpec& c, const float* packed, i
     ex.fail(mcvc_igemm_launch(g, ex.s));
 }
 
-// the direct kernels are next, and the last re-pack skipped the copies they read (pack_skips bit 0 / bit 1): fail the pass instead
-static bool stale_direct(Exec& ex, const ConvSpec& c)
-{
-    if (ex.dry || !(((ex.pack_skips & 1) && c.off_tk >= 0) || ((ex.pack_skips & 2) && (c.wino || c.wino3)))) return false;
-    ex.fail(MCVC_ERR_INVALID);
-    return true;
-}
-
 static void conv_fwd(Exec& ex, const ConvSpec& c, const float* packed, int NB, int H, int W, CView x, View y, long long y_total,
                      int shuffle, int allow_split, int* nsplit)
 {
@@ -719,19 +607,19 @@ static void conv_fwd(Exec& ex, const ConvSpec& c, const float* packed, int NB, i
         const int sp = (allow_split && nsplit) ? sgemm_split(c.cout_tot, NT, KT) : 1;       // slabs 1.. are summed by the consumer (norm / act)
         const long long slab_need = (long long)(sp - 1) * y_total;
         if (ex.dry) { if (slab_need > ex.slab_need) ex.slab_need = slab_need; if (nsplit) *nsplit = sp; return; }
-        if ((ex.pack_skips & 1) && c.off_tk >= 0) { ex.fail(MCVC_ERR_INVALID); return; }     // stale K-major copy
+        if (stale(ex, c, PF_FWD)) return;
         if (!b_in_place && slab_need <= ex.slab_cap && y.sh == sk.OW && y.sc == P && (NB == 1 || y.sb == (long long)c.cout_tot * P)) {
             // 1 x 3 over dense rows: an implicit GEMM (sgemm.h) -- the three windows of x are gathered where they lie, shifted by -1 / 0 / +1
             // column; the K-major forward copy's rows are (ci, kw), so a tap's rows are KW apart
             IGemmArgs g{};
             g.ncls = 1;
             IGemmClass& q = g.cls[0];
-            q.a = packed + c.off_fwd; q.ntaps = c.KW; q.coff = 0;
+            q.a = packed + c.off[PF_FWD]; q.ntaps = c.KW; q.coff = 0;
             for (int kw = 0; kw < c.KW; ++kw) { q.boff[kw] = kw - c.pw; q.aoff[kw] = (long long)kw * c.cout_pk; q.zs[kw] = kw < c.pw ? 1 : (kw > c.pw ? 2 : 0); }
             g.a_ks = (long long)c.KW * c.cout_pk; g.zw = W;
             g.b = x.p; g.b_cs = x.sc; g.b_sn = x.sb; g.b_pitch = x.sh; g.Cb = c.Cin; g.OW = W; g.P = P;
             g.c = y.p; g.ldc = y.sc; g.c_sn = y.sb; g.c_sh = y.sh; g.c_sw = 1;
-            g.bias = packed + c.off_bias;
+            g.bias = packed + c.off[PF_BIAS];
             g.M = c.cout_tot; g.N = (int)NT; g.nsplit = sp; g.c_slab = ex.slabs; g.c_split = y_total;
             ex.fail(mcvc_igemm_launch(g, ex.s));
             if (nsplit) *nsplit = sp;
@@ -740,10 +628,10 @@ static void conv_fwd(Exec& ex, const ConvSpec& c, const float* packed, int NB, i
         if (b_in_place && x.sh == W && x.sc == P && slab_need <= ex.slab_cap && y.sh == sk.OW && y.sc == P &&
             (NB == 1 || y.sb == (long long)c.cout_tot * P)) {
             SGemmArgs g{};
-            g.a = packed + c.off_fwd; g.lda = c.cout_pk;                       // Wt[k = ci][co] (value | gate columns)
+            g.a = packed + c.off[PF_FWD]; g.lda = c.cout_pk;                       // Wt[k = ci][co] (value | gate columns)
             g.b = x.p; g.ldb = x.sc; g.bseg = P; g.b_sn = x.sb;
             g.c = y.p; g.ldc = y.sc; g.cseg = P; g.c_sn = y.sb;
-            g.bias = packed + c.off_bias;
+            g.bias = packed + c.off[PF_BIAS];
             g.M = c.cout_tot; g.N = (int)NT; g.K = KT; g.nsplit = sp; g.c_slab = ex.slabs; g.c_split = y_total;
             ex.fail(mcvc_sgemm_launch(g, ex.s));
             if (nsplit) *nsplit = sp;
@@ -751,14 +639,14 @@ static void conv_fwd(Exec& ex, const ConvSpec& c, const float* packed, int NB, i
         }
     }
     if (conv_wino(ex, c, packed, 0, NB, H, W, x, y, shuffle, 0) || (!shuffle && conv_wino3(ex, c, packed, 0, NB, H, W, x, y, 0))) { if (nsplit) *nsplit = 1; return; }
-    if (stale_direct(ex, c)) return;
+    if (stale(ex, c, PF_FWD)) return;          // the direct kernels are next
     ConvProblem p{c.Cin, H, W, c.cout_tot, conv_out(H, c.KH, c.stride, c.ph), conv_out(W, c.KW, c.stride, c.pw),
                   c.KH, c.KW, c.stride, c.ph, c.pw};
     ConvIO io{};
     io.x = x.p; io.x_sb = x.sb; io.x_sc = x.sc; io.x_sh = x.sh;
     io.y = y.p; io.y_sb = y.sb; io.y_sc = y.sc; io.y_sh = y.sh; io.y_sw = 1;
     io.shuffle = shuffle;
-    run_conv(ex, p, NB, io, y_total, packed + c.off_fwd, c.w_rows, c.cout_pk, packed + c.off_bias, allow_split, 0, nsplit);
+    run_conv(ex, p, NB, io, y_total, packed + c.off[PF_FWD], c.w_rows, c.cout_pk, packed + c.off[PF_BIAS], allow_split, 0, nsplit);
 }
 
 // dX = conv-backward-data.  dy: conv-output layout (cout_tot channels, OHxOW); dx: input layout.
@@ -782,12 +670,12 @@ static void conv_dgrad(Exec& ex, const ConvSpec& c, const float* packed, int NB,
         if (slab_need > ex.slab_need) ex.slab_need = slab_need;
         if (nsplit) *nsplit = slab_all ? sp + 1 : sp;
         if (ex.dry) return;
-        if ((ex.pack_skips & 1) && c.off_tk >= 0) { ex.fail(MCVC_ERR_INVALID); return; }     // stale K-major copy
+        if (stale(ex, c, PF_FWD)) return;
         if (slab_need > ex.slab_cap) { ex.fail(MCVC_ERR_WORKSPACE); return; }
         IGemmArgs g{};
         g.ncls = 1;
         IGemmClass& q = g.cls[0];
-        q.a = packed + c.off_fwd; q.ntaps = c.KW; q.coff = 0;
+        q.a = packed + c.off[PF_FWD]; q.ntaps = c.KW; q.coff = 0;
         for (int kw = 0; kw < c.KW; ++kw) {
             const int sh = c.pw - kw;                 // dX[n] += W[:, :, kw]^T dY[n + pw - kw]
             q.boff[kw] = sh; q.aoff[kw] = (long long)kw * c.cout_pk; q.zs[kw] = sh < 0 ? 1 : (sh > 0 ? 2 : 0);
@@ -802,21 +690,20 @@ static void conv_dgrad(Exec& ex, const ConvSpec& c, const float* packed, int NB,
         return;
     }
     if (conv_wino3(ex, c, packed, 1, NB, H, W, dy, dx, accumulate)) { if (nsplit) *nsplit = 1; return; }
-    if (stale_direct(ex, c)) return;
-    if (!ex.dry && (ex.pack_skips & 8) && c.stride == 2) { ex.fail(MCVC_ERR_INVALID); return; }      // (mcvc_disc_pack_small: these copies are stale)
     static const int ucls_nb = mcvc_knob("MCVC_DGRAD_CLASSES_NB", 8);
-    const bool per_class = c.merged && c.off_dcls >= 0 && NB >= ucls_nb;
+    const bool per_class = c.merged && c.off[PF_DCLS] >= 0 && NB >= ucls_nb;
+    if (stale(ex, c, per_class ? PF_DCLS : PF_DGRAD)) return;          // the direct kernels are next
     if (c.merged && !per_class) {
         ConvProblem p{c.cout_tot, OH, OW, 4 * c.Cin, (H + 1) / 2, (W + 1) / 2, c.mg_kh, c.mg_kw, 1, c.mg_pad_h, c.mg_pad_w};
         ConvIO io{};
         io.x = dy.p; io.x_sb = dy.sb; io.x_sc = dy.sc; io.x_sh = dy.sh;
         io.y = dx.p; io.y_sb = dx.sb; io.y_sc = dx.sc; io.y_sh = dx.sh; io.y_sw = 1;
         io.accumulate = accumulate; io.shuffle = 1; io.YH = H; io.YW = W;
-        run_conv(ex, p, NB, io, dx_total, packed + c.off_dgrad, c.dg_rows_co * c.mg_kh * c.mg_kw, c.mg_ld, nullptr, allow_split, 0, nsplit);
+        run_conv(ex, p, NB, io, dx_total, packed + c.off[PF_DGRAD], c.dg_rows_co * c.mg_kh * c.mg_kw, c.mg_ld, nullptr, allow_split, 0, nsplit);
         return;
     }
     const DgradClass* klass = per_class ? c.ucls : c.cls;
-    const long long kbase = per_class ? c.off_dcls : c.off_dgrad;
+    const long long kbase = c.off[per_class ? PF_DCLS : PF_DGRAD];
     ConvProblem ps[4];
     int force = 0;
     for (int k = 0; k < c.ncls; ++k) {
@@ -934,8 +821,8 @@ static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, int NB,
             return nbc != 0;
         };
         // (MCVC_WINO_WGRAD switches the 36-point form only)
-        if (c.wino) done = (wino4_applies(ex, c, NB, H, W) && attempt(kWino[kF45], 1, 32)) || attempt(kWino[kF25], en25, 0);
-        else done = (wino43_applies(ex, c, NB, OH, OW) && attempt(kWino[kF43], en3, 32)) || attempt(kWino[kF23], en3, 0);
+        if (c.wino) done = (wino4_applies(ex, c, NB, H, W, false) && attempt(kWino[kF45], 1, 32)) || attempt(kWino[kF25], en25, 0);
+        else done = (wino43_applies(ex, c, NB, OH, OW, false) && attempt(kWino[kF43], en3, 32)) || attempt(kWino[kF23], en3, 0);
     }
     if (!done && c.cout_tot == 1 && mcvc_wgrad_cout1_applies(p) && grads[c.wi[0]]) {       // one output channel: VALU kernel
         WgradIO io{x.p, x.sb, x.sc, x.sh, dy.p, dy.sb, dy.sc, dy.sh};
@@ -970,146 +857,45 @@ static void conv_bias_grad(Exec& ex, const ConvSpec& c, float* const* grads, int
     }
 }
 
-static void pack_spec(Exec& ex, const ConvSpec& c, const float* const* params, float* packed)
+// ---- whole-network pack: job tables (packforms.h) built once per plan, resident on the device ---------------------
+// A plan: which forms of which layers of which network a table refreshes, in table order.  It is the cache key of the device tables -- a
+// comparable VALUE, so two different plans never share a table -- and what the staleness records are set from.
+struct PackPlan {
+    int dev = 0, net = 0, update = 0;                  // net: 0 generator, 1 discriminator, 2 one op-level layer of `shape`
+    int sets = 3;                                      // 1: the forms a forward pass reads, 2: those only a backward pass reads, 3: both
+    std::array<int, 8> shape{};
+    std::vector<std::pair<int, unsigned>> layers;      // (ConvSpec::index, forms)
+    void add(const ConvSpec& c, unsigned forms) { layers.emplace_back(c.index, forms & spec_forms(c)); }
+    bool operator<(const PackPlan& o) const
+    { return std::tie(dev, net, update, sets, shape, layers) < std::tie(o.dev, o.net, o.update, o.sets, o.shape, o.layers); }
+};
+static PackTable build_table(const PackPlan& k, const ConvSpec* const* specs)
 {
-    const int K = c.Cin * c.KH * c.KW;
-    for (int br = 0; br < c.nbr; ++br) {
-        const float* w = params[c.wi[br]];
-        ex.fail(mcvc_pack_fwd_launch(w, packed + c.off_fwd, c.Cout, K, c.cout_pk, br * c.Cout, ex.s));
-        ex.fail(mcvc_copy_launch(params[c.bi[br]], packed + c.off_bias + br * c.Cout, c.Cout, ex.s));
-        PackDgradArgs a{};
-        a.Cin = c.Cin; a.KH = c.KH; a.KW = c.KW; a.step = c.stride; a.ld = c.merged ? c.mg_ld : c.cin_pk; a.co_off = br * c.Cout; a.ncls = c.ncls;
-        a.merged = c.merged; a.mg_kh = c.mg_kh; a.mg_kw = c.mg_kw;
-        for (int k = 0; k < c.ncls; ++k) a.cls[k] = c.cls[k];
-        ex.fail(mcvc_pack_dgrad_launch(w, packed + c.off_dgrad, a, c.Cout, ex.s));
-        if (c.off_tk >= 0) ex.fail(mcvc_pack_trunk_t_launch(w, packed + c.off_tk, c.Cout, c.Cin, c.KW, c.cout_tot * c.KW, br * c.Cout, ex.s));
-    }
+    PackTable t;
+    t.sides = side_forms(k.sets);
+    for (const auto& lf : k.layers) add_spec_jobs(t, *specs[lf.first], lf.second);
+    return t;
 }
-
-// ---- whole-network pack: job table built once per network kind, resident on the device ---------------------
-struct PackTable { std::vector<PackJob> jobs; std::vector<PackDgradArgs> dga; int nblocks = 0; double bytes = 0.0, wbytes = 0.0; };     // wbytes: the written share
-
-static void add_job(PackTable& t, PackJob j, int gx, int gy)
+// the re-pack of plan k was issued on `packed`: its layers' records become the forms it refreshes (sets = 2 adds them to a forward-only refresh)
+static void record_fresh(const void* packed, const PackPlan& k)
 {
-    j.block0 = t.nblocks; j.gx = gx;
-    t.nblocks += gx * gy;
-    t.jobs.push_back(j);
-}
-
-// trunk_only: the layer runs on the fused trunk kernels (OIHW forward); only the transposed data-gradient copy is needed
-// wino_only: the layer runs on the Winograd kernels in every pass (forward, data-gradient); its direct K-major copies are skipped
-// sets: 1 = the copies a FORWARD pass reads (K-major forward copies, biases, forward Winograd sets), 2 = the copies only a BACKWARD pass
-// reads (data-gradient copies, transposed trunk copies, data-gradient Winograd sets), 3 = both
-// igemm_only: the layer runs on the implicit-GEMM kernels in every pass (the discriminators' stride-2 layers): only the bias, the tap-major
-// forward copy and the per-class data-gradient copies are refreshed
-static void add_spec_jobs(PackTable& t, const ConvSpec& c, bool trunk_only = false, bool wino_only = false, int sets = 3, bool w4 = true, bool w43 = true,
-                          bool igemm_only = false, bool w2 = true)
-{
-    const int K = c.Cin * c.KH * c.KW;
-    const bool fw = (sets & 1) != 0, bw = (sets & 2) != 0;
-    for (int br = 0; br < c.nbr; ++br) {
-        // (on leaving this iteration: every weight job it added carries its tensor's geometry -- the fused update's tiles, build_upd_table)
-        struct Geo { PackTable& t; const ConvSpec& c; size_t first;
-                     ~Geo() { for (size_t q = first; q < t.jobs.size(); ++q) if (t.jobs[q].kind != PACK_COPY) {
-                                  PackJob& j = t.jobs[q]; j.Cout = c.Cout; j.Cin = c.Cin; j.taps = c.KH * c.KW; } } } geo{t, c, t.jobs.size()};
-        const bool skip_direct = (wino_only && (c.wino || c.wino3)) || (igemm_only && c.igemm);
-        if (trunk_only && c.off_tk >= 0) {
-            if (!bw) continue;
-            PackJob q{}; q.kind = PACK_TRUNK_T; q.param = c.wi[br]; q.dst = c.off_tk; q.Cout = c.Cout; q.Cin = c.Cin; q.KW = c.KW;
-            q.ld = c.cout_tot * c.KW; q.co_off = br * c.Cout;
-            add_job(t, q, cdiv_i(c.Cin, 32), cdiv_i(c.Cout, 32));
-            t.bytes += 8.0 * c.Cout * K; t.wbytes += 4.0 * c.Cout * K;
-            continue;
-        }
-        PackJob f{}; f.kind = PACK_FWD; f.param = c.wi[br]; f.dst = c.off_fwd; f.Cout = c.Cout; f.K = K; f.ld = c.cout_pk; f.co_off = br * c.Cout;
-        if (!skip_direct && fw) add_job(t, f, cdiv_i(K, 32), cdiv_i(c.Cout, 32));
-        PackJob b{}; b.kind = PACK_COPY; b.param = c.bi[br]; b.dst = c.off_bias + br * c.Cout; b.Cout = c.Cout;
-        if (fw) add_job(t, b, cdiv_i(c.Cout, 256), 1);
-        PackDgradArgs a{};
-        a.Cin = c.Cin; a.KH = c.KH; a.KW = c.KW; a.step = c.stride; a.ld = c.merged ? c.mg_ld : c.cin_pk; a.co_off = br * c.Cout; a.ncls = c.ncls;
-        a.merged = c.merged; a.mg_kh = c.mg_kh; a.mg_kw = c.mg_kw;
-        for (int k = 0; k < c.ncls; ++k) a.cls[k] = c.cls[k];
-        PackJob d{}; d.kind = PACK_DGRAD; d.param = c.wi[br]; d.dst = c.off_dgrad; d.dg = (int)t.dga.size();
-        if (!skip_direct && bw) {
-            t.dga.push_back(a);
-            add_job(t, d, cdiv_i(c.Cin, 32), c.Cout);
-        }
-        if (c.off_dcls >= 0 && bw && !(igemm_only && c.igemm)) {          // exact per-class copies (large-batch data-gradient of the 3x3 stride-2 layers)
-            PackDgradArgs u = a;
-            u.merged = 0; u.ld = c.cin_pk;
-            for (int k = 0; k < c.ncls; ++k) u.cls[k] = c.ucls[k];
-            PackJob du{}; du.kind = PACK_DGRAD; du.param = c.wi[br]; du.dst = c.off_dcls; du.dg = (int)t.dga.size();
-            t.dga.push_back(u);
-            add_job(t, du, cdiv_i(c.Cin, 32), c.Cout);
-            t.bytes += 4.0 * 2.0 * c.Cout * K; t.wbytes += 4.0 * c.Cout * K;
-        }
-        if (c.off_tk >= 0 && bw) {
-            PackJob q{}; q.kind = PACK_TRUNK_T; q.param = c.wi[br]; q.dst = c.off_tk; q.Cout = c.Cout; q.Cin = c.Cin; q.KW = c.KW;
-            q.ld = c.cout_tot * c.KW; q.co_off = br * c.Cout;
-            add_job(t, q, cdiv_i(c.Cin, 32), cdiv_i(c.Cout, 32));
-        }
-        if (c.igemm && (sets & 4) == 0) {                   // (sets bit 2: skip the implicit-GEMM copies)
-            PackJob fi{}; fi.kind = PACK_FWD_TAP; fi.param = c.wi[br]; fi.dst = c.off_ifwd; fi.Cout = c.Cout; fi.K = K; fi.ld = c.cout_pk;
-            fi.co_off = br * c.Cout; fi.KW = c.KH * c.KW;
-            if (fw) add_job(t, fi, cdiv_i(K, 32), cdiv_i(c.Cout, 32));
-            t.bytes += 4.0 * fw * 2.0 * c.Cout * K; t.wbytes += 4.0 * fw * c.Cout * K;
-        }
-        if (c.wino3) {
-            PackJob w3{}; w3.kind = PACK_WINO3_D; w3.param = c.wi[br]; w3.dst = c.off_w3; w3.Cout = c.Cout; w3.Cin = c.Cin; w3.ld = c.mg_ld;
-            w3.xi_stride = c.w3_xi; w3.co_off = br * c.Cout;
-            if (bw) add_job(t, w3, cdiv_i(c.Cin, 256), c.Cout);
-            PackJob w3f{}; w3f.kind = PACK_WINO3_F; w3f.param = c.wi[br]; w3f.dst = c.off_w3f; w3f.Cout = c.Cout; w3f.Cin = c.Cin; w3f.ld = c.cout_pk;
-            w3f.xi_stride = c.w3f_xi; w3f.co_off = br * c.Cout;
-            if (fw) add_job(t, w3f, cdiv_i(c.Cout, 256), c.Cin);
-            t.bytes += 4.0 * (fw + bw) * (25.0 + 64.0) * c.Cout * c.Cin; t.wbytes += 4.0 * (fw + bw) * 64.0 * c.Cout * c.Cin;
-        }
-        if (c.wino3 && w43) {
-            PackJob w3{}; w3.kind = PACK_WINO43_D; w3.param = c.wi[br]; w3.dst = c.off_w43; w3.Cout = c.Cout; w3.Cin = c.Cin; w3.ld = c.mg_ld;
-            w3.xi_stride = c.w3_xi; w3.co_off = br * c.Cout;
-            if (bw) add_job(t, w3, cdiv_i(c.Cin, 256), c.Cout);
-            PackJob w3f{}; w3f.kind = PACK_WINO43_F; w3f.param = c.wi[br]; w3f.dst = c.off_w43f; w3f.Cout = c.Cout; w3f.Cin = c.Cin; w3f.ld = c.cout_pk;
-            w3f.xi_stride = c.w3f_xi; w3f.co_off = br * c.Cout;
-            if (fw) add_job(t, w3f, cdiv_i(c.Cout, 256), c.Cin);
-            t.bytes += 4.0 * (fw + bw) * (25.0 + 144.0) * c.Cout * c.Cin; t.wbytes += 4.0 * (fw + bw) * 144.0 * c.Cout * c.Cin;
-        }
-        if (c.wino && w4) {
-            PackJob wf{}; wf.kind = PACK_WINO4_F; wf.param = c.wi[br]; wf.dst = c.off_w4f; wf.Cout = c.Cout; wf.Cin = c.Cin; wf.ld = c.cout_pk;
-            wf.xi_stride = c.wf_xi; wf.co_off = br * c.Cout;
-            if (fw) add_job(t, wf, cdiv_i(c.Cout, 256), c.Cin);
-            PackJob wd{}; wd.kind = PACK_WINO4_D; wd.param = c.wi[br]; wd.dst = c.off_w4d; wd.Cout = c.Cout; wd.Cin = c.Cin; wd.ld = c.cin_pk;
-            wd.xi_stride = c.wd_xi; wd.co_off = br * c.Cout;
-            if (bw) add_job(t, wd, cdiv_i(c.Cin, 256), c.Cout);
-            t.bytes += 4.0 * (fw + bw) * (25.0 + 64.0) * c.Cout * c.Cin; t.wbytes += 4.0 * (fw + bw) * 64.0 * c.Cout * c.Cin;
-        }
-        if (c.wino && w2) {
-            PackJob wf{}; wf.kind = PACK_WINO_F; wf.param = c.wi[br]; wf.dst = c.off_wf; wf.Cout = c.Cout; wf.Cin = c.Cin; wf.ld = c.cout_pk;
-            wf.xi_stride = c.wf_xi; wf.co_off = br * c.Cout;
-            if (fw) add_job(t, wf, cdiv_i(c.Cout, 256), c.Cin);
-            PackJob wd{}; wd.kind = PACK_WINO_D; wd.param = c.wi[br]; wd.dst = c.off_wd; wd.Cout = c.Cout; wd.Cin = c.Cin; wd.ld = c.cin_pk;
-            wd.xi_stride = c.wd_xi; wd.co_off = br * c.Cout;
-            if (bw) add_job(t, wd, cdiv_i(c.Cin, 256), c.Cout);
-            t.bytes += 4.0 * (fw + bw) * (25.0 + 36.0) * c.Cout * c.Cin; t.wbytes += 4.0 * (fw + bw) * 36.0 * c.Cout * c.Cin;
-        }
-        t.bytes += skip_direct ? 8.0 * c.Cout : 4.0 * ((c.off_tk >= 0 ? 6.0 : 4.0) * c.Cout * K + 2.0 * c.Cout);
-        t.wbytes += skip_direct ? 4.0 * c.Cout : 4.0 * ((c.off_tk >= 0 ? 3.0 : 2.0) * c.Cout * K + c.Cout);
-    }
+    std::lock_guard<std::mutex> lk(g_pack_mu);
+    PackFresh& r = g_pack_fresh[packed];               // (a buffer never seen starts fully fresh)
+    for (const auto& lf : k.layers) r.layer[lf.first] = (k.sets == 2 ? r.layer[lf.first] : 0u) | (lf.second & side_forms(k.sets));
 }
 
 struct DevPackTable { PackJob* jobs; PackDgradArgs* dga; int njobs, nblocks; double bytes; std::vector<int> used; };
 
-// one upload per (device, network kind); the first call must happen outside stream capture (it allocates)
-template <class Build>
-static const DevPackTable* dev_pack_table(int kind, Build&& build, int* err)
+// one upload per (device, plan); the first call must happen outside stream capture (it allocates)
+static const DevPackTable* dev_pack_table(PackPlan k, const ConvSpec* const* specs, int* err)
 {
     static std::mutex mu;
-    static std::map<std::pair<int, int>, DevPackTable> cache;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { *err = MCVC_ERR_INVALID; return nullptr; }
+    static std::map<PackPlan, DevPackTable> cache;
+    if (hipGetDevice(&k.dev) != hipSuccess) { *err = MCVC_ERR_INVALID; return nullptr; }
     std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find({dev, kind});
+    auto it = cache.find(k);
     if (it != cache.end()) return &it->second;
-    PackTable t;
-    build(t);
+    PackTable t = build_table(k, specs);
     DevPackTable d{};
     d.njobs = (int)t.jobs.size(); d.nblocks = t.nblocks; d.bytes = t.bytes;
     hipError_t e = hipMalloc((void**)&d.jobs, t.jobs.size() * sizeof(PackJob));
@@ -1118,7 +904,7 @@ static const DevPackTable* dev_pack_table(int kind, Build&& build, int* err)
     if (e == hipSuccess) e = hipMemcpy(d.dga, t.dga.data(), t.dga.size() * sizeof(PackDgradArgs), hipMemcpyHostToDevice);
     if (e != hipSuccess) { *err = (int)e; return nullptr; }
     for (const PackJob& j : t.jobs) d.used.push_back(j.param);
-    return &cache.emplace(std::make_pair(dev, kind), std::move(d)).first->second;
+    return &cache.emplace(std::move(k), std::move(d)).first->second;
 }
 
 static int pack_net(const DevPackTable* t, const float* const* params, float* packed, hipStream_t s)
@@ -1129,49 +915,40 @@ static int pack_net(const DevPackTable* t, const float* const* params, float* pa
 }
 
 // ---- optimizer step fused with the re-pack (pack.h: UpdOwner) -----------------------------------------------------------------------
-// The job table of a re-pack (same `build` as dev_pack_table) is re-grouped by parameter: every tensor of the parameter range gets ONE owner
+// The job table of a re-pack (same plan as dev_pack_table) is re-grouped by parameter: every tensor of the parameter range gets ONE owner
 // -- a tiled owner whose workgroups update a (CB x IB x taps) block of filters and emit all packed forms of that block, or a flat owner
 // (biases, norm affine parameters, tensors nothing is packed from) -- so that one launch is optimizer.step() AND the refresh of every
 // copy the kernels read (reference train.py:242,299).
 struct DevUpdTable { UpdOwner* owners; PackJob* jobs; PackDgradArgs* dga; int nown, nblocks; double adam_floats, pack_bytes; std::vector<int> used;
                      std::vector<long long> sizes; };      // sizes[k]: element count of parameter used[k] the tiles were built for
 
-template <class Build, class InRange>
-static const DevUpdTable* dev_upd_table(int kind, Build&& build, const long long* numel, int nparams, InRange&& in_range, int* err)
+// host half: the owners and the re-ordered jobs (no device call)
+struct UpdPlan { std::vector<UpdOwner> owners; std::vector<PackJob> jobs; int nblocks = 0; double adam_floats = 0.0; std::vector<int> used; std::vector<long long> sizes; };
+static int plan_upd(const PackTable& t, const long long* numel, int nparams, const std::vector<char>& in_range, UpdPlan& u)
 {
-    static std::mutex mu;
-    static std::map<std::pair<int, int>, DevUpdTable> cache;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { *err = MCVC_ERR_INVALID; return nullptr; }
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find({dev, kind});
-    if (it != cache.end()) return &it->second;
-    PackTable t;
-    build(t);
-    std::vector<PackJob> jobs;                  // re-ordered: the emits of one parameter are consecutive
-    std::vector<UpdOwner> owners;
-    DevUpdTable d{};
+    std::vector<PackJob>& jobs = u.jobs;                  // re-ordered: the emits of one parameter are consecutive
+    std::vector<UpdOwner>& owners = u.owners;
     int nblocks = 0;
     for (int prm = 0; prm < nparams && prm < 128; ++prm) {
         std::vector<PackJob> mine;
         for (const PackJob& j : t.jobs) if (j.param == prm) mine.push_back(j);
-        if (!in_range(prm)) { if (!mine.empty()) { *err = MCVC_ERR_INVALID; return nullptr; } continue; }
-        if (numel[prm] <= 0) { if (!mine.empty()) { *err = MCVC_ERR_INVALID; return nullptr; } continue; }       // (dead parameter)
+        if (!in_range[prm]) { if (!mine.empty()) return MCVC_ERR_INVALID; continue; }
+        if (numel[prm] <= 0) { if (!mine.empty()) return MCVC_ERR_INVALID; continue; }       // (dead parameter)
         UpdOwner o{};
         o.param = prm; o.block0 = nblocks; o.e0 = (int)jobs.size(); o.ne = (int)mine.size();
         bool weight = false;
         for (const PackJob& j : mine) weight = weight || j.kind != PACK_COPY;
         if (!weight) {
             o.flat = 1; o.Cout = (int)numel[prm]; o.Cin = o.taps = 1; o.gx = 1;
-            for (const PackJob& j : mine) if (j.Cout != o.Cout) { *err = MCVC_ERR_INVALID; return nullptr; }
+            for (const PackJob& j : mine) if (j.Cout != o.Cout) return MCVC_ERR_INVALID;
             nblocks += cdiv_i(o.Cout, 256);
         } else {
             const PackJob& j0 = mine[0];
             o.Cout = j0.Cout; o.Cin = j0.Cin; o.taps = j0.taps;
-            for (const PackJob& j : mine) if (j.kind == PACK_COPY || j.Cout != o.Cout || j.Cin != o.Cin || j.taps != o.taps) { *err = MCVC_ERR_INVALID; return nullptr; }
+            for (const PackJob& j : mine) if (j.kind == PACK_COPY || j.Cout != o.Cout || j.Cin != o.Cin || j.taps != o.taps) return MCVC_ERR_INVALID;
             // (the Winograd weight transforms read ONE 5 x 5 filter = 25 consecutive LDS words: upd_emit_filters)
-            for (const PackJob& j : mine) if (j.kind >= PACK_WINO_F && j.kind <= PACK_WINO43_F && j.taps != 25) { *err = MCVC_ERR_INVALID; return nullptr; }
-            if ((long long)o.Cout * o.Cin * o.taps != numel[prm]) { *err = MCVC_ERR_INVALID; return nullptr; }
+            for (const PackJob& j : mine) if (j.kind >= PACK_WINO_F && j.kind <= PACK_WINO43_F && j.taps != 25) return MCVC_ERR_INVALID;
+            if ((long long)o.Cout * o.Cin * o.taps != numel[prm]) return MCVC_ERR_INVALID;
             // tile: 32 x 16 filters of 25 taps (the Winograd layers: two filters per thread), 32 x 32 of 9, 32 x 64 of 3, 32 x 128 of 1;
             // the 5 x 15 edge layers (2 input channels / 1 output channel) as they come
             int cb = 32, ib = 32;
@@ -1183,29 +960,46 @@ static const DevUpdTable* dev_upd_table(int kind, Build&& build, const long long
             else if (o.taps == 1) ib = 128;
             else if (o.taps > 25) ib = 16;
             o.CB = cb < o.Cout ? cb : o.Cout; o.IB = ib < o.Cin ? ib : o.Cin;
-            if ((size_t)o.CB * mcvc_upd_pitch(o.IB, o.taps) * sizeof(float) > kUpdLds) { *err = MCVC_ERR_INVALID; return nullptr; }
+            if ((size_t)o.CB * mcvc_upd_pitch(o.IB, o.taps) * sizeof(float) > kUpdLds) return MCVC_ERR_INVALID;
             o.vec4 = ((o.IB * o.taps) % 4 == 0 && (o.Cin % o.IB) == 0 && ((long long)o.Cin * o.taps) % 4 == 0) ? 1 : 0;
             o.gx = cdiv_i(o.Cin, o.IB);
             nblocks += o.gx * cdiv_i(o.Cout, o.CB);
         }
-        d.adam_floats += (double)numel[prm];
+        u.adam_floats += (double)numel[prm];
         for (const PackJob& j : mine) jobs.push_back(j);
         owners.push_back(o);
-        d.used.push_back(prm); d.sizes.push_back(numel[prm]);
+        u.used.push_back(prm); u.sizes.push_back(numel[prm]);
     }
-    if (jobs.size() != t.jobs.size() || owners.empty()) { *err = MCVC_ERR_INVALID; return nullptr; }
-    d.nown = (int)owners.size(); d.nblocks = nblocks;
+    if (jobs.size() != t.jobs.size() || owners.empty()) return MCVC_ERR_INVALID;
+    u.nblocks = nblocks;
+    return 0;
+}
+
+static const DevUpdTable* dev_upd_table(PackPlan k, const ConvSpec* const* specs, const long long* numel, int nparams, const std::vector<char>& in_range, int* err)
+{
+    static std::mutex mu;
+    static std::map<PackPlan, DevUpdTable> cache;
+    if (hipGetDevice(&k.dev) != hipSuccess) { *err = MCVC_ERR_INVALID; return nullptr; }
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find(k);
+    if (it != cache.end()) return &it->second;
+    PackTable t = build_table(k, specs);
+    UpdPlan u;
+    if (int e = plan_upd(t, numel, nparams, in_range, u)) { *err = e; return nullptr; }
+    DevUpdTable d{};
+    d.adam_floats = u.adam_floats; d.used = u.used; d.sizes = u.sizes;
+    d.nown = (int)u.owners.size(); d.nblocks = u.nblocks;
     d.pack_bytes = t.wbytes;
-    if (jobs.empty()) jobs.push_back(PackJob{});
+    if (u.jobs.empty()) u.jobs.push_back(PackJob{});
     if (t.dga.empty()) t.dga.push_back(PackDgradArgs{});
-    hipError_t e = hipMalloc((void**)&d.owners, owners.size() * sizeof(UpdOwner));
-    if (e == hipSuccess) e = hipMalloc((void**)&d.jobs, jobs.size() * sizeof(PackJob));
+    hipError_t e = hipMalloc((void**)&d.owners, u.owners.size() * sizeof(UpdOwner));
+    if (e == hipSuccess) e = hipMalloc((void**)&d.jobs, u.jobs.size() * sizeof(PackJob));
     if (e == hipSuccess) e = hipMalloc((void**)&d.dga, t.dga.size() * sizeof(PackDgradArgs));
-    if (e == hipSuccess) e = hipMemcpy(d.owners, owners.data(), owners.size() * sizeof(UpdOwner), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d.jobs, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d.owners, u.owners.data(), u.owners.size() * sizeof(UpdOwner), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d.jobs, u.jobs.data(), u.jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d.dga, t.dga.data(), t.dga.size() * sizeof(PackDgradArgs), hipMemcpyHostToDevice);
     if (e != hipSuccess) { *err = (int)e; return nullptr; }
-    return &cache.emplace(std::make_pair(dev, kind), std::move(d)).first->second;
+    return &cache.emplace(std::move(k), std::move(d)).first->second;
 }
 
 // the optimizer arguments of the fused update: the gradient(s) and the moments live at the same offsets of their flat buffers as the
@@ -1286,7 +1080,7 @@ struct TrunkPre {              // fused InstanceNorm backward in front of the da
 static bool trunk_dgrad(Exec& ex, const ConvSpec& c, const float* packed, const float* dy, float* dx, int accumulate, int B, int W4,
                         int* nsplit = nullptr, const TrunkPre* pre = nullptr)
 {
-    if (!trunk_enabled() || c.off_tk < 0) return false;
+    if (!trunk_enabled() || c.off[PF_TRUNK_T] < 0) return false;
     int ks = 1;
     if (!accumulate && mcvc_trunk_applies(c.cout_tot, c.KW, c.Cin, B, W4, TRUNK_PLAIN, 1)) ks = 1;
     else ks = trunk_pick_ksplit(c.cout_tot, c.KW, c.Cin, B, W4, 0);
@@ -1303,7 +1097,7 @@ static bool trunk_dgrad(Exec& ex, const ConvSpec& c, const float* packed, const 
     if (nsplit) *nsplit = slab_all ? ks + 1 : (accumulate ? 1 : ks);
     if (ex.dry) return true;
     TrunkArgs a{};
-    a.a0 = packed + c.off_tk;
+    a.a0 = packed + c.off[PF_TRUNK_T];
     a.x = dy; a.x_sc = (long long)B * W4; a.x_sb = W4;
     a.Cin = c.cout_tot; a.KW = c.KW; a.K = c.cout_tot * c.KW; a.M = c.Cin; a.Mtot = c.Cin; a.B = B; a.T4 = W4; a.N = B * W4;
     a.conv_out = dx; a.c_sc = (long long)B * W4; a.c_sb = W4; a.accumulate = accumulate; a.mode = TRUNK_PLAIN;
@@ -1422,6 +1216,13 @@ struct GenNet {
     long long packed_floats;
 };
 
+// the layers in ConvSpec::index order = their order in the packed buffer
+static void gen_layers(const GenNet& g, const ConvSpec** l)
+{
+    const ConvSpec* head[] = {&g.conv1, &g.ds1, &g.ds2, &g.c2d1d, &g.c1d2d, &g.up1, &g.up2, &g.last};
+    for (int i = 0; i < 8; ++i) l[i] = head[i];
+    for (int i = 0; i < 6; ++i) { l[8 + 2 * i] = &g.res_vg[i]; l[9 + 2 * i] = &g.res_out[i]; }
+}
 static GenNet build_gen()
 {
     GenNet g{};
@@ -1439,13 +1240,20 @@ static GenNet build_gen()
     g.up1 = mk(256, 1024, 1, 5, 5, 1, 2, 2, 104, 105, -1, -1, 1);       // :192-196 (PixelShuffle before the norm -> bias grad live)
     g.up2 = mk(256, 512, 1, 5, 5, 1, 2, 2, 100, 101, -1, -1, 1);        // :200-204 (named convLayer.* in named_parameters)
     g.last = mk(128, 1, 1, 5, 15, 1, 2, 7, 108, 109, -1, -1, 1);        // :207-211
-    ConvSpec* all[] = {&g.conv1, &g.ds1, &g.ds2, &g.c2d1d, &g.c1d2d, &g.up1, &g.up2, &g.last};
-    for (ConvSpec* c : all) spec_finalize(*c, cur);
-    for (int i = 0; i < 6; ++i) { spec_finalize(g.res_vg[i], cur); spec_finalize(g.res_out[i], cur); }
+    const ConvSpec* l[kMaxLayers];
+    gen_layers(g, l);
+    for (int i = 0; i < kMaxLayers; ++i) { ConvSpec& c = const_cast<ConvSpec&>(*l[i]); c.index = i; spec_finalize(c, cur); }      // (g itself is not const)
     g.packed_floats = cur;
     return g;
 }
 static const GenNet& gen_net() { static const GenNet g = build_gen(); return g; }
+static const ConvSpec* const* gen_specs()
+{
+    static const ConvSpec* l[kMaxLayers];
+    static const bool once = (gen_layers(gen_net(), l), true);
+    (void)once;
+    return l;
+}
 
 struct GenDims {
     int B, T, W2, W4, Wu1, Wu2;
@@ -1744,7 +1552,7 @@ static void gen_backward_impl(Exec& ex, const float* const* P, const float* pack
     bool bwd_net = bwd_net_knob && trunk_bwd_net_enabled() && fuse_knob && trunk_enabled() && batch_w && !ex.dry && G && ex.sync &&
                    mcvc_trunk_bwd_net_applies(B, W4);
     for (int i = 0; i < 6 && bwd_net; ++i)
-        bwd_net = g.res_out[i].off_tk >= 0 && g.res_vg[i].off_tk >= 0 && mcvc_trunk_applies(g.res_out[i].cout_tot, 3, g.res_out[i].Cin, B, W4, TRUNK_PLAIN, 1);
+        bwd_net = g.res_out[i].off[PF_TRUNK_T] >= 0 && g.res_vg[i].off[PF_TRUNK_T] >= 0 && mcvc_trunk_applies(g.res_out[i].cout_tot, 3, g.res_out[i].Cin, B, W4, TRUNK_PLAIN, 1);
     if (bwd_net) {
         TrunkBwdNetArgs na{};
         int l = 0;
@@ -1754,12 +1562,12 @@ static void gen_backward_impl(Exec& ex, const float* const* P, const float* pack
             float* dt3 = sc + q.dtx3 + (long long)i * 256 * BT4;
             float* dt1 = sc + q.dtx1 + (long long)i * 1024 * BT4;
             TrunkBwdLayerDesc& da = na.L[l++];           // conv1d_out_layer (512 -> 256) + its InstanceNorm: d(h_out) -> d(GLU output)
-            da.wt = packed + g.res_out[i].off_tk; da.dy = DH; da.px = st + o.r[i].cb; da.stats = st + o.r[i].sb;
+            da.wt = packed + g.res_out[i].off[PF_TRUNK_T]; da.dy = DH; da.px = st + o.r[i].cb; da.stats = st + o.r[i].sb;
             da.g0 = P[b + 10]; da.b0 = P[b + 11]; da.xout = dt3; da.pxB = pxB; da.dg0 = G[b + 10]; da.db0 = G[b + 11];
             da.out = DT2; da.pre = 1; da.C = 256; da.M = 512; da.rows = 8;
             da.flags = (i < 5 ? TBWD_DY_FRESH : 0) | ((i == 5 && ns > 1) ? TBWD_SLAB_DY : 0);            // (conv1dto2d's K-split slabs)
             TrunkBwdLayerDesc& db = na.L[l++];           // value | gate convs (256 -> 512 each) + norms + GLU: d(GLU output) -> d(h_in), added to the skip path
-            db.wt = packed + g.res_vg[i].off_tk; db.dy = DT2; db.px = st + o.r[i].ca; db.stats = st + o.r[i].sa;
+            db.wt = packed + g.res_vg[i].off[PF_TRUNK_T]; db.dy = DT2; db.px = st + o.r[i].ca; db.stats = st + o.r[i].sa;
             db.g0 = P[b + 2]; db.b0 = P[b + 3]; db.g1 = P[b + 6]; db.b1 = P[b + 7]; db.xout = dt1; db.pxB = pxB;
             db.dg0 = G[b + 2]; db.db0 = G[b + 3]; db.dg1 = G[b + 6]; db.db1 = G[b + 7];
             db.out = DH; db.pre = 2; db.C = 512; db.M = 256; db.rows = 4;
@@ -1777,7 +1585,7 @@ static void gen_backward_impl(Exec& ex, const float* const* P, const float* pack
         const int b = 24 + 12 * i;
         const float* hin = (i == 0) ? (st + o.y4) : (st + o.r[i - 1].y);
         DT3 = DT3s[i & 1]; DT1 = DT1s[i & 1];
-        const bool fuse = fuse_knob && trunk_enabled() && ns == 1 && !ex.dry && G && g.res_out[i].off_tk >= 0 && g.res_vg[i].off_tk >= 0 &&
+        const bool fuse = fuse_knob && trunk_enabled() && ns == 1 && !ex.dry && G && g.res_out[i].off[PF_TRUNK_T] >= 0 && g.res_vg[i].off[PF_TRUNK_T] >= 0 &&
                           mcvc_trunk_applies(g.res_out[i].cout_tot, 3, g.res_out[i].Cin, B, W4, TRUNK_PLAIN, 1) &&
                           trunk_pick_ksplit(g.res_vg[i].cout_tot, 3, g.res_vg[i].Cin, B, W4, 0) >= 1;
         if (fuse) {
@@ -1887,13 +1695,19 @@ static DiscNet build_disc()
     n.ds[1] = mk(256, 512, 1, 3, 3, 2, 1, 1, 6, 7, -1, -1, 0);           // :304-308
     n.ds[2] = mk(512, 1024, 1, 3, 3, 2, 1, 1, 10, 11, -1, -1, 0);        // :310-314
     n.outc = mk(1024, 1, 1, 1, 3, 1, 0, 1, 18, 19, -1, -1, 1);           // :323-327   (downSample4, params 14-17, is dead: :316-320 never called)
-    spec_finalize(n.conv1, cur);
-    for (int i = 0; i < 3; ++i) spec_finalize(n.ds[i], cur);
-    spec_finalize(n.outc, cur);
+    ConvSpec* all[] = {&n.conv1, &n.ds[0], &n.ds[1], &n.ds[2], &n.outc};
+    int k = 0;
+    for (ConvSpec* c : all) { c->index = k++; spec_finalize(*c, cur); }
     n.packed_floats = cur;
     return n;
 }
 static const DiscNet& disc_net() { static const DiscNet n = build_disc(); return n; }
+static const ConvSpec* const* disc_specs()
+{
+    static const DiscNet& n = disc_net();
+    static const ConvSpec* const v[] = {&n.conv1, &n.ds[0], &n.ds[1], &n.ds[2], &n.outc};
+    return v;
+}
 
 struct DiscDims { int B, T, H[4], W[4]; long long big; };
 static DiscDims disc_dims(int B, int T)
@@ -2195,18 +2009,27 @@ long long mcvc_disc_scratch_floats(int B, int T)
     return disc_scratch(disc_dims(B, T)).slabs + nd.slab + nd.sg + nd.sgw + nd.wslab + 64;
 }
 
-int mcvc_gen_pack(const float* const* params, float* packed, void* stream)
+// every form of every layer, in layer order
+static PackPlan full_plan(int net, const ConvSpec* const* specs, int nlayers)
+{
+    PackPlan k;
+    k.net = net;
+    for (int l = 0; l < nlayers; ++l) k.add(*specs[l], kAllForms);
+    return k;
+}
+static int pack_plan_run(const PackPlan& k, const ConvSpec* const* specs, const float* const* params, float* packed, void* stream)
 {
     int err = 0;
-    const DevPackTable* t = dev_pack_table(0, [](PackTable& pt) {
-        const GenNet& g = gen_net();
-        const ConvSpec* all[] = {&g.conv1, &g.ds1, &g.ds2, &g.c2d1d, &g.c1d2d, &g.up1, &g.up2, &g.last};
-        for (const ConvSpec* c : all) add_spec_jobs(pt, *c);
-        for (int i = 0; i < 6; ++i) { add_spec_jobs(pt, g.res_vg[i]); add_spec_jobs(pt, g.res_out[i]); }
-    }, &err);
-    if (!t) return err;
-    set_pack_skips(packed, 0);
+    const DevPackTable* t = dev_pack_table(k, specs, &err);
+    if (!t) return err ? err : MCVC_ERR_INVALID;
+    record_fresh(packed, k);
+    if (t->njobs == 0) return 0;
     return pack_net(t, params, packed, (hipStream_t)stream);
+}
+
+int mcvc_gen_pack(const float* const* params, float* packed, void* stream)
+{
+    return pack_plan_run(full_plan(0, gen_specs(), kMaxLayers), gen_specs(), params, packed, stream);
 }
 
 // 1 if every 1-D layer of a generator pass with batch B at T frames takes the fused trunk path (see trunk_fwd / trunk_dgrad)
@@ -2242,8 +2065,8 @@ int mcvc_gen_trunk_persistent(int B, int T)
     return m;
 }
 
-// `sets`: 1 = only what a forward pass reads, 2 = only what a backward pass reads, 3 = both (see add_spec_jobs).  After a forward-only
-// refresh the backward sets are marked stale (bit 2 of the registry) and a backward pass on this buffer fails until sets = 2 has run.
+// `sets`: 1 = only what a forward pass reads, 2 = only what a backward pass reads, 3 = both (PackSide).  After a forward-only
+// refresh no backward form of the layers is fresh and a backward pass on this buffer fails until sets = 2 has run.
 int mcvc_gen_pack_sets(const float* const* params, float* packed, int max_batch, int T, int sets, void* stream)
 {
     return mcvc_gen_pack_ranges(params, packed, max_batch, T, sets, 7, stream);
@@ -2252,7 +2075,7 @@ int mcvc_gen_pack_sets(const float* const* params, float* packed, int max_batch,
 // ... restricted to the layers of some parameter ranges (bit 0: upSample1/2 + lastConvLayer = parameters [100,110); bit 1: the residual
 // blocks + conv1dto2d = [24,100); bit 2: conv1, downSample1/2, conv2dto1d = [0,24) -- the ranges whose gradients become final one after the
 // other during a backward pass, mcvc_gen_backward_overlap): the optimizer step + re-pack of a range can then run beside the rest of the pass
-struct GenPackCfg { bool fused, wino_only, w4, w43, up1_w4, up1_w2, up2_w2; int skipped; };
+struct GenPackCfg { bool fused, wino_only, w4, w43, up1_w4, up1_w2, up2_w2; };
 static GenPackCfg gen_pack_cfg(int max_batch, int T)
 {
     GenPackCfg q{};
@@ -2266,17 +2089,16 @@ static GenPackCfg gen_pack_cfg(int max_batch, int T)
     const GenDims dm = gen_dims(max_batch, T);
     const bool wino_default = knobs_default && !g_precise;
     q.wino_only = q.fused && wino_default && (T % 4) == 0 && T >= 32 && (long long)max_batch * 20 * dm.W4 <= 16384;
-    // the 64-point weight sets of upSample1/2 only when some pass can take the F(4x4,5x5) path (wino4_applies); otherwise marked absent (bit 16)
+    // the 64-point weight sets of upSample1/2 only when some pass can take the F(4x4,5x5) path (wino4_applies); otherwise not written
     q.w4 = wino_default && wino4_min_nb() > 0 && max_batch >= wino4_min_nb() && (T % 16) == 0;
-    q.w43 = wino_default && wino43_min_nb() > 0 && max_batch >= wino43_min_nb() && (T % 16) == 0;      // (bit 32)
+    q.w43 = wino_default && wino43_min_nb() > 0 && max_batch >= wino43_min_nb() && (T % 16) == 0;
     q.up1_w4 = (long long)max_batch * 5 * (T / 16) >= wino4_min_tiles();             // upSample1 runs on 20 x T/4 images: 5 x T/16 tiles per sample
     // the 36-point sets of a layer only where some pass still runs F(2x2,5x5): a layer with >= wino4_min_tiles() tiles PER SAMPLE (upSample2
     // at 64 frames: 80) takes the 4 x 4 scheme in every pass, forward, data gradient and weight gradient (wino4_applies), so its 36-point
-    // sets -- 2 x 36/25 of its weights per step -- have no reader (bit 128; r5)
+    // sets -- 2 x 36/25 of its weights per step -- have no reader (r5)
     const bool all4 = q.w4 && wino4_min_nb() == 1;
     q.up1_w2 = !(all4 && 5LL * (T / 16) >= wino4_min_tiles());
     q.up2_w2 = !(all4 && 10LL * (T / 8) >= wino4_min_tiles());
-    q.skipped = (q.fused ? (q.wino_only ? 3 : 1) : 0) | (q.w4 ? 0 : 16) | (q.w43 ? 0 : 32) | (q.up1_w2 ? 0 : 128) | (q.up2_w2 ? 0 : 256);
     return q;
 }
 // range_mask bits: 1 = parameters [100,110), 2 = [24,100), 4 = [0,24); r4: the head in three parts, in the order their gradients become final
@@ -2287,44 +2109,36 @@ static bool gen_in_range(int m, int p)
     return ((m & 1) && p >= 100 && p < 110) || ((m & 2) && p >= 24 && p < 100) || ((m & 4) && p < 24) ||
            ((m & 8) && p >= 12 && p < 24) || ((m & 16) && p >= 4 && p < 12) || ((m & 32) && p < 4);
 }
-static void gen_pack_build(PackTable& pt, const GenPackCfg& q, int sets, int range_mask)
+static PackPlan gen_pack_build(const GenPackCfg& q, int sets, int range_mask, int update)
 {
     const GenNet& g = gen_net();
-    if (range_mask & (4 | 32)) add_spec_jobs(pt, g.conv1, false, q.wino_only, sets, q.w4, q.w43);
-    if (range_mask & (4 | 16)) add_spec_jobs(pt, g.ds1, false, q.wino_only, sets, q.w4, q.w43);
-    if (range_mask & (4 | 8)) {
-        add_spec_jobs(pt, g.ds2, false, q.wino_only, sets, q.w4, q.w43);
-        add_spec_jobs(pt, g.c2d1d, q.fused, false, sets);
-    }
+    PackPlan k;
+    k.net = 0; k.update = update; k.sets = sets;
+    const unsigned w4 = form_bit(PF_W4F) | form_bit(PF_W4D), w43 = form_bit(PF_W43F) | form_bit(PF_W43D), w2 = form_bit(PF_W2F) | form_bit(PF_W2D);
+    auto conv2d = [&](const ConvSpec& c, bool c_w4, bool c_w2) {
+        k.add(c, (q.wino_only ? wino_only_forms(c) : kAllForms) & ~((c_w4 ? 0 : w4) | (q.w43 ? 0 : w43) | (c_w2 ? 0 : w2)));
+    };
+    auto trunk = [&](const ConvSpec& c) { k.add(c, q.fused ? trunk_fused_forms(c) : kAllForms); };
+    if (range_mask & (4 | 32)) conv2d(g.conv1, q.w4, true);
+    if (range_mask & (4 | 16)) conv2d(g.ds1, q.w4, true);
+    if (range_mask & (4 | 8)) { conv2d(g.ds2, q.w4, true); trunk(g.c2d1d); }
     if (range_mask & 1) {
-        const ConvSpec* up[] = {&g.up1, &g.up2, &g.last};
         // (a layer whose largest pass has fewer than 64 F(4x4) tiles never takes that path, conv_wino4: its 64-point sets are not written)
-        for (const ConvSpec* c : up) add_spec_jobs(pt, *c, false, q.wino_only, sets, q.w4 && (c != &g.up1 || q.up1_w4), q.w43, false,
-                                                   c == &g.up1 ? q.up1_w2 : (c == &g.up2 ? q.up2_w2 : true));
+        conv2d(g.up1, q.w4 && q.up1_w4, q.up1_w2);
+        conv2d(g.up2, q.w4, q.up2_w2);
+        conv2d(g.last, q.w4, true);
     }
     if (range_mask & 2) {
-        add_spec_jobs(pt, g.c1d2d, q.fused, false, sets);
-        for (int i = 0; i < 6; ++i) { add_spec_jobs(pt, g.res_vg[i], q.fused, false, sets); add_spec_jobs(pt, g.res_out[i], q.fused, false, sets); }
+        trunk(g.c1d2d);
+        for (int i = 0; i < 6; ++i) { trunk(g.res_vg[i]); trunk(g.res_out[i]); }
     }
-}
-static int gen_pack_key(const GenPackCfg& q, int sets, int range_mask)
-{
-    return 16 + 4 * sets + (q.fused ? (q.wino_only ? 3 : 2) : 0) + 64 * range_mask /* <= 63 */ + (q.w4 ? 4096 : 0) + (q.w43 ? 8192 : 0) + (q.up1_w4 ? 16384 : 0) +
-           (q.up1_w2 ? 0 : 32768) + (q.up2_w2 ? 0 : 65536);
+    return k;
 }
 
 int mcvc_gen_pack_ranges(const float* const* params, float* packed, int max_batch, int T, int sets, int range_mask, void* stream)
 {
     if (sets < 1 || sets > 3 || !gen_range_mask_ok(range_mask)) return MCVC_ERR_INVALID;
-    const GenPackCfg q = gen_pack_cfg(max_batch, T);
-    int err = 0;
-    const DevPackTable* t = dev_pack_table(gen_pack_key(q, sets, range_mask), [&](PackTable& pt) { gen_pack_build(pt, q, sets, range_mask); }, &err);
-    if (!t) return err;
-    if (sets == 1) set_pack_skips(packed, q.skipped | 4);
-    else if (sets == 2) set_pack_skips(packed, get_pack_skips(packed) & ~4);
-    else set_pack_skips(packed, q.skipped);
-    if (t->njobs == 0) return 0;
-    return pack_net(t, params, packed, (hipStream_t)stream);
+    return pack_plan_run(gen_pack_build(gen_pack_cfg(max_batch, T), sets, range_mask, 0), gen_specs(), params, packed, stream);
 }
 
 // optimizer.step() of a generator's parameter ranges (train.py:242) fused with the refresh of every packed copy derived from them: ONE
@@ -2336,14 +2150,13 @@ int mcvc_gen_update_ranges(const float* const* params, const long long* numel, f
                            float eps, int step, float grad_scale, int zero_grads, void* stream)
 {
     if (!params || !numel || !packed || !gen_range_mask_ok(range_mask)) return MCVC_ERR_INVALID;
-    const GenPackCfg q = gen_pack_cfg(max_batch, T);
+    const PackPlan k = gen_pack_build(gen_pack_cfg(max_batch, T), 3, range_mask, 1);
     int err = MCVC_ERR_INVALID;
-    auto in_range = [range_mask](int p) { return gen_in_range(range_mask, p); };
-    const DevUpdTable* t = dev_upd_table(gen_pack_key(q, 3, range_mask), [&](PackTable& pt) { gen_pack_build(pt, q, 3, range_mask); }, numel, MCVC_GEN_NPARAMS,
-                                         in_range, &err);
+    std::vector<char> in_range(MCVC_GEN_NPARAMS);
+    for (int p = 0; p < MCVC_GEN_NPARAMS; ++p) in_range[p] = gen_in_range(range_mask, p);
+    const DevUpdTable* t = dev_upd_table(k, gen_specs(), numel, MCVC_GEN_NPARAMS, in_range, &err);
     if (!t) return err;
-    // (a range's update leaves ITS copies fresh; the registry word describes which KINDS of copies exist, as after a full re-pack)
-    set_pack_skips(packed, q.skipped);
+    record_fresh(packed, k);          // (a range's update leaves the forms of ITS layers fresh)
     return update_net(t, params, numel, packed, UpdOpt{flat, grad, grad2, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale, zero_grads}, (hipStream_t)stream);
 }
 
@@ -2354,53 +2167,34 @@ int mcvc_gen_pack_small_batch(const float* const* params, float* packed, int max
 
 int mcvc_disc_pack(const float* const* params, float* packed, void* stream)
 {
-    int err = 0;
-    const DevPackTable* t = dev_pack_table(1, [](PackTable& pt) {
-        const DiscNet& n = disc_net();
-        add_spec_jobs(pt, n.conv1);
-        for (int i = 0; i < 3; ++i) add_spec_jobs(pt, n.ds[i]);
-        add_spec_jobs(pt, n.outc);
-    }, &err);
-    if (!t) return err;
-    set_pack_skips(packed, 0);
-    return pack_net(t, params, packed, (hipStream_t)stream);
+    return pack_plan_run(full_plan(1, disc_specs(), 5), disc_specs(), params, packed, stream);
 }
 
 // Discriminator re-pack restricted to what the implicit-GEMM schedule reads: of the three stride-2 layers (99.9 % of the weights) only the
 // tap-major FORWARD copy + bias -- it serves the forward pass and, read row-major, the data gradient (sgemm.h arow); the weight gradient reads
 // no weights at all; the first / output layers (tiny) are refreshed in full.  Falls back to the full pack when a layer would not take that
-// path at T frames.  The direct kernels' data-gradient copies are then marked stale (bit 8) and refuse to run.
+// path at T frames.  The direct kernels' copies of those layers are then not fresh and refuse to run.
 int mcvc_disc_pack_small(const float* const* params, float* packed, int T, void* stream) { return mcvc_disc_pack_batch(params, packed, 1, T, stream); }
 
-// which job table a discriminator re-pack for passes of up to max_batch samples uses: 1 = full, 4 = implicit GEMMs; `skips` = the registry
-// word it leaves
-static int disc_pack_kind(int max_batch, int T, int* skips)
+// which job table a discriminator re-pack for passes of up to max_batch samples uses: 1 = full, 4 = implicit GEMMs
+static int disc_pack_kind(int max_batch, int T)
 {
-    const DiscDims d = disc_dims(max_batch < 1 ? 1 : max_batch, T);
-    if (disc_igemm(d)) { *skips = 8; return 4; }
-    *skips = 0;
-    return 1;
+    return disc_igemm(disc_dims(max_batch < 1 ? 1 : max_batch, T)) ? 4 : 1;
 }
-static void disc_pack_build(PackTable& pt, int kind)
+static PackPlan disc_pack_build(int kind, int update)
 {
     const DiscNet& n = disc_net();
-    add_spec_jobs(pt, n.conv1);
-    for (int i = 0; i < 3; ++i) {
-        if (kind == 1) add_spec_jobs(pt, n.ds[i]);
-        else add_spec_jobs(pt, n.ds[i], false, false, 1, true, true, true);
-    }
-    add_spec_jobs(pt, n.outc);
+    PackPlan k;
+    k.net = 1; k.update = update;
+    k.add(n.conv1, kAllForms);
+    for (int i = 0; i < 3; ++i) k.add(n.ds[i], kind == 1 ? kAllForms : igemm_only_forms(n.ds[i]));
+    k.add(n.outc, kAllForms);
+    return k;
 }
 
 int mcvc_disc_pack_batch(const float* const* params, float* packed, int max_batch, int T, void* stream)
 {
-    int skips = 0, err = 0;
-    const int kind = disc_pack_kind(max_batch, T, &skips);
-    if (kind == 1) { set_pack_skips(packed, 0); return mcvc_disc_pack(params, packed, stream); }
-    const DevPackTable* t = dev_pack_table(kind, [kind](PackTable& pt) { disc_pack_build(pt, kind); }, &err);
-    if (!t) return err;
-    set_pack_skips(packed, skips);
-    return pack_net(t, params, packed, (hipStream_t)stream);
+    return pack_plan_run(disc_pack_build(disc_pack_kind(max_batch, T), 0), disc_specs(), params, packed, stream);
 }
 
 // optimizer.step() of one discriminator (train.py:299) fused with the refresh of its packed copies; arguments as mcvc_gen_update_ranges
@@ -2410,12 +2204,94 @@ int mcvc_disc_update_batch(const float* const* params, const long long* numel, f
                            float eps, int step, float grad_scale, int zero_grads, void* stream)
 {
     if (!params || !numel || !packed) return MCVC_ERR_INVALID;
-    int skips = 0, err = MCVC_ERR_INVALID;
-    const int kind = disc_pack_kind(max_batch, T, &skips);
-    const DevUpdTable* t = dev_upd_table(kind, [kind](PackTable& pt) { disc_pack_build(pt, kind); }, numel, MCVC_DISC_NPARAMS, [](int) { return true; }, &err);
+    const PackPlan k = disc_pack_build(disc_pack_kind(max_batch, T), 1);
+    int err = MCVC_ERR_INVALID;
+    const DevUpdTable* t = dev_upd_table(k, disc_specs(), numel, MCVC_DISC_NPARAMS, std::vector<char>(MCVC_DISC_NPARAMS, 1), &err);
     if (!t) return err;
-    set_pack_skips(packed, skips);
+    record_fresh(packed, k);
     return update_net(t, params, numel, packed, UpdOpt{flat, grad, grad2, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale, zero_grads}, (hipStream_t)stream);
+}
+
+// ---- host view of a pack / update plan (no device call): one row of kPlanW 64-bit integers per record (include/mcvc.h) ---------------------
+namespace {
+constexpr int kPlanW = 20;
+struct PlanRows {
+    long long* rows; int cap, n = 0;
+    void put(std::initializer_list<long long> v)
+    {
+        if (n < cap) { long long* r = rows + (long long)n * kPlanW; int i = 0; for (long long x : v) r[i++] = x; for (; i < kPlanW; ++i) r[i] = 0; }
+        ++n;
+    }
+};
+static long long dbits(double d) { long long b; memcpy(&b, &d, sizeof(b)); return b; }
+// element counts of a network's parameter tensors: the convolutions' from their specs, the norm affine pairs that follow a convolution
+static void net_numel(const ConvSpec* const* specs, int n, long long* numel)
+{
+    for (int l = 0; l < n; ++l) {
+        const ConvSpec& c = *specs[l];
+        const bool edge = l == 0 || c.Cout == 1;                        // conv1 / the last layer: no norm behind them
+        for (int br = 0; br < c.nbr; ++br) {
+            numel[c.wi[br]] = (long long)c.Cout * c.Cin * c.KH * c.KW; numel[c.bi[br]] = c.Cout;
+            if (!edge) numel[c.wi[br] + 2] = numel[c.wi[br] + 3] = c.wino ? c.Cout / 4 : c.Cout;      // (upSample1/2: PixelShuffle(2) before the norm)
+        }
+    }
+}
+}  // namespace
+
+int mcvc_pack_plan(int net, int max_batch, int T, int sets, int range_mask, int update, long long* rows, int cap, int* n_rows)
+{
+    if (!n_rows || (net != 0 && net != 1) || (update != 0 && update != 1) || max_batch < 1 || T < 1 || sets < 1 || sets > 3 || (update && sets != 3) ||
+        cap < 0 || (cap > 0 && !rows)) return MCVC_ERR_INVALID;
+    if (net == 0 ? !gen_range_mask_ok(range_mask) : range_mask != 7) return MCVC_ERR_INVALID;
+    const ConvSpec* const* specs = net == 0 ? gen_specs() : disc_specs();
+    const int nl = net == 0 ? kMaxLayers : 5, nparams = net == 0 ? MCVC_GEN_NPARAMS : MCVC_DISC_NPARAMS;
+    long long cfg = 0;
+    PackPlan k;
+    if (net == 0) {
+        const GenPackCfg q = gen_pack_cfg(max_batch, T);
+        cfg = q.fused | q.wino_only << 1 | q.w4 << 2 | q.w43 << 3 | q.up1_w4 << 4 | q.up1_w2 << 5 | q.up2_w2 << 6;
+        k = gen_pack_build(q, sets, range_mask, update);
+    } else {
+        cfg = disc_pack_kind(max_batch, T);
+        k = disc_pack_build((int)cfg, update);
+    }
+    const PackTable t = build_table(k, specs);
+    UpdPlan u;
+    if (update) {
+        long long numel[128] = {};
+        net_numel(specs, nl, numel);
+        std::vector<char> in_range(nparams, 1);
+        if (net == 0) for (int p = 0; p < nparams; ++p) in_range[p] = gen_in_range(range_mask, p);
+        if (int e = plan_upd(t, numel, nparams, in_range, u)) return e;
+    }
+    const std::vector<PackJob>& jobs = update ? u.jobs : t.jobs;
+    PlanRows R{rows, cap};
+    R.put({0, net, update, (long long)jobs.size(), (long long)u.owners.size(), (long long)t.dga.size(), update ? u.nblocks : t.nblocks,
+           net == 0 ? gen_net().packed_floats : disc_net().packed_floats, dbits(t.bytes), dbits(t.wbytes), cfg, kPlanW});
+    for (const PackJob& j : jobs) {
+        int layer = -1, form = -1;
+        for (int l = 0; l < nl && layer < 0; ++l)          // whose form the job writes: the one of its kind that holds dst
+            for (int f = 0; f < kNumForms; ++f) {
+                const long long o = specs[l]->off[f];
+                if (o >= 0 && kPackForms[f].kind == j.kind && j.dst >= o && j.dst < o + form_floats(*specs[l], (PackForm)f)) { layer = l; form = f; }
+            }
+        if (layer < 0) return MCVC_ERR_INVALID;
+        const long long len = j.kind == PACK_COPY ? j.Cout : form_floats(*specs[layer], (PackForm)form);
+        R.put({1, layer, form, j.kind, j.param, j.dst, len, j.block0, j.gx, j.Cout, j.Cin, j.K, j.ld, j.co_off, j.KW, j.taps, j.xi_stride, j.dg});
+    }
+    for (const UpdOwner& o : u.owners) R.put({2, o.param, o.block0, o.gx, o.Cout, o.Cin, o.taps, o.CB, o.IB, o.e0, o.ne, o.flat, o.vec4});
+    std::sort(k.layers.begin(), k.layers.end());
+    for (const auto& lf : k.layers) R.put({3, lf.first, sets, lf.second & side_forms(sets)});      // what record_fresh would note
+    for (size_t i = 0; i < t.dga.size(); ++i) {
+        const PackDgradArgs& a = t.dga[i];
+        R.put({4, (long long)i, a.Cin, a.KH, a.KW, a.step, a.ld, a.co_off, a.merged, a.mg_kh, a.mg_kw, a.ncls, a.tapmajor, a.cout_rows});
+        for (int c = 0; c < a.ncls; ++c) {
+            const DgradClass& d = a.cls[c];
+            R.put({5, (long long)i, c, d.nth, d.ntw, d.khmax, d.kwmax, d.pad_h, d.pad_w, d.qh, d.qw, d.su, d.sv, d.offset});
+        }
+    }
+    *n_rows = R.n;
+    return R.n > cap ? MCVC_ERR_WORKSPACE : 0;
 }
 
 int mcvc_gen_forward(const float* const* params, const float* packed, const float* x, const float* mask, float* out, float* stash,
@@ -2428,7 +2304,7 @@ int mcvc_gen_forward(const float* const* params, const float* packed, const floa
     if (ex.wslab_cap < 0) return MCVC_ERR_WORKSPACE;
     { const GenScratch q = gen_scratch(d); ex.wv = scratch + q.wv; ex.wm = scratch + q.wm; ex.wino_cap = q.wino_floats;
       ex.sync = reinterpret_cast<unsigned*>(scratch + q.sync); }
-    ex.pack_skips = get_pack_skips(packed);
+    ex.fresh = get_fresh(packed);
     gen_forward_impl(ex, params, packed, x, mask, out, stash, d);
     return ex.err;
 }
@@ -2485,8 +2361,9 @@ int mcvc_gen_backward_window(const float* const* params, const float* packed, fl
     { const GenScratch q = gen_scratch(d); ex.wv = scratch + q.wv; ex.wm = scratch + q.wm; ex.wino_cap = q.wino_floats;
       ex.wv2 = scratch + q.wv2; ex.wm2 = scratch + q.wm2; ex.wu = scratch + q.wu; ex.wu_cap = q.wu_floats;
       ex.sync = reinterpret_cast<unsigned*>(scratch + q.sync); }
-    ex.pack_skips = get_pack_skips(packed);
-    if (ex.pack_skips & 4) return MCVC_ERR_INVALID;          // forward-only re-pack: the backward sets are stale (mcvc_gen_pack_sets)
+    ex.fresh = get_fresh(packed);
+    for (int l = 0; l < kMaxLayers; ++l)          // forward-only re-pack of a layer: none of its backward forms is fresh (mcvc_gen_pack_sets)
+        if (!(ex.fresh.layer[l] & spec_forms(*gen_specs()[l]) & side_forms(PACK_SIDE_BWD))) return MCVC_ERR_INVALID;
     ex.no_join = (flags & 1) && aux_stream;
     ex.fine_ms = (flags & 2) != 0;
     gen_backward_impl(ex, params, packed, grads, mask, dout, dx, accumulate_dx, stash, scratch, d, milestones, stash_B, stash_b0);
@@ -2508,7 +2385,7 @@ int mcvc_disc_forward(const float* const* params, const float* packed, const flo
     const DiscDims d = disc_dims(B, T);
     Exec ex = make_exec(stream, nullptr, scratch, scratch_floats, disc_scratch(d).slabs, disc_needs(B, T));
     if (ex.wslab_cap < 0) return MCVC_ERR_WORKSPACE;
-    ex.pack_skips = get_pack_skips(packed);
+    ex.fresh = get_fresh(packed);
     // keep the input for the first layer's weight gradient
     ex.fail(mcvc_copy_launch(x, stash + disc_stash(d).total, B * 80 * T, ex.s));
     disc_forward_impl(ex, params, packed, x, out, stash, d);
@@ -2523,7 +2400,7 @@ int mcvc_disc_backward(const float* const* params, const float* packed, float* c
     const DiscDims d = disc_dims(B, T);
     Exec ex = make_exec(stream, aux_stream, scratch, scratch_floats, disc_scratch(d).slabs, disc_needs(B, T));
     if (ex.wslab_cap < 0) return MCVC_ERR_WORKSPACE;
-    ex.pack_skips = get_pack_skips(packed);
+    ex.fresh = get_fresh(packed);
     disc_backward_impl(ex, params, packed, grads, dout, dout_is_logit_grad, dx, accumulate_dx, stash, scratch, d);
     return ex.err;
 }
@@ -2725,7 +2602,7 @@ static ConvSpec single_spec(int Cout, int Cin, int KH, int KW, int stride, int p
     ConvSpec c = mk(Cin, Cout, 1, KH, KW, stride, ph, pw, 0, 1, -1, -1, 1);
     long long cur = 0;
     spec_finalize(c, cur);
-    c.off_dcls = -1;               // (the single-op pack holds the merged matrix only)
+    c.off[PF_DCLS] = -1;               // (the single-op pack holds the merged matrix only)
     return c;
 }
 
@@ -2746,8 +2623,8 @@ int mcvc_conv2d_forward(const float* x, const float* w, const float* bias, float
     if (stride != 1 && stride != 2) return MCVC_ERR_INVALID;
     const ConvSpec c = single_spec(Cout, Cin, KH, KW, stride, pad_h, pad_w);
     Exec ex{}; ex.s = (hipStream_t)stream;
-    ex.fail(mcvc_pack_fwd_launch(w, wpack + c.off_fwd, Cout, Cin * KH * KW, c.cout_pk, 0, ex.s));
-    if (bias) ex.fail(mcvc_copy_launch(bias, wpack + c.off_bias, Cout, ex.s));
+    ex.fail(mcvc_pack_fwd_launch(w, wpack + c.off[PF_FWD], Cout, Cin * KH * KW, c.cout_pk, 0, ex.s));
+    if (bias) ex.fail(mcvc_copy_launch(bias, wpack + c.off[PF_BIAS], Cout, ex.s));
     const int OH = conv_out(H, KH, stride, pad_h), OW = conv_out(W, KW, stride, pad_w);
     const long long y_total = (long long)N * Cout * OH * OW;
     ex.slabs = slabs; ex.slab_cap = slabs ? (long long)(max_slabs - 1) * y_total : 0; ex.max_split = max_slabs > 0 ? max_slabs : 1;
@@ -2759,7 +2636,7 @@ int mcvc_conv2d_forward(const float* x, const float* w, const float* bias, float
     io.y = yv.p; io.y_sb = yv.sb; io.y_sc = yv.sc; io.y_sh = yv.sh; io.y_sw = 1; io.shuffle = pixel_shuffle;
     int want = (slabs && max_slabs > 1) ? mcvc_conv_plan_nsplit(p, N, 1) : 1;
     if (want > max_slabs) want = max_slabs;
-    run_conv(ex, p, N, io, y_total, wpack + c.off_fwd, c.w_rows, c.cout_pk, bias ? wpack + c.off_bias : nullptr, 0, want, &ns);
+    run_conv(ex, p, N, io, y_total, wpack + c.off[PF_FWD], c.w_rows, c.cout_pk, bias ? wpack + c.off[PF_BIAS] : nullptr, 0, want, &ns);
     if (ns > 1) act_fwd(ex, y, y_total, ns, nullptr, 1, 1, (int)y_total, ACT_NONE);
     return ex.err;
 }
@@ -2770,11 +2647,7 @@ int mcvc_conv2d_dgrad(const float* dy, const float* w, float* dx, float* wpack, 
     if (stride != 1 && stride != 2) return MCVC_ERR_INVALID;
     const ConvSpec c = single_spec(Cout, Cin, KH, KW, stride, pad_h, pad_w);
     Exec ex{}; ex.s = (hipStream_t)stream;
-    PackDgradArgs a{};
-    a.Cin = Cin; a.KH = KH; a.KW = KW; a.step = stride; a.ld = c.merged ? c.mg_ld : c.cin_pk; a.co_off = 0; a.ncls = c.ncls;
-    a.merged = c.merged; a.mg_kh = c.mg_kh; a.mg_kw = c.mg_kw;
-    for (int k = 0; k < c.ncls; ++k) a.cls[k] = c.cls[k];
-    ex.fail(mcvc_pack_dgrad_launch(w, wpack + c.off_dgrad, a, Cout, ex.s));
+    ex.fail(mcvc_pack_dgrad_launch(w, wpack + c.off[PF_DGRAD], dgrad_args(c, 0), Cout, ex.s));
     const int OH = conv_out(H, KH, stride, pad_h), OW = conv_out(W, KW, stride, pad_w);
     const long long dx_total = (long long)N * Cin * H * W;
     ex.slabs = slabs; ex.slab_cap = slabs ? (long long)(max_slabs - 1) * dx_total : 0; ex.max_split = max_slabs > 0 ? max_slabs : 1;
@@ -2904,10 +2777,12 @@ int mcvc_layer_pack(const float* w0, const float* b0, const float* w1, const flo
     if (!w0 || !b0 || !packed || branches < 1 || branches > 2 || (branches == 2 && (!w1 || !b1))) return MCVC_ERR_INVALID;
     const LayerCtx l = layer_ctx(Cin, Cout, branches, KH, KW, stride, pad_h, pad_w);
     // the job table of this layer alone (cached per device and layer shape like the networks' tables)
-    const long long h = (((((((long long)Cin * 31 + Cout) * 31 + branches) * 31 + KH) * 31 + KW) * 31 + stride) * 31 + pad_h) * 31 + pad_w;
-    const int key = 1000 + (int)(h % 1000003);
+    PackPlan k;
+    k.net = 2; k.shape = {Cin, Cout, branches, KH, KW, stride, pad_h, pad_w};
+    k.add(l.c, kAllForms);
+    const ConvSpec* spec = &l.c;
     int err = 0;
-    const DevPackTable* t = dev_pack_table(key, [&](PackTable& pt) { add_spec_jobs(pt, l.c); }, &err);
+    const DevPackTable* t = dev_pack_table(k, &spec, &err);
     if (!t) return err ? err : MCVC_ERR_INVALID;
     const float* params[4] = {w0, b0, w1, b1};
     return pack_net(t, params, packed, (hipStream_t)stream);

@@ -92,6 +92,7 @@ _SIGS = {
                                        c_float, c_float, c_float, c_float, c_int, c_float, c_int, c_void_p]),
     "mcvc_disc_update_batch": (c_int, [_PP, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_float, c_float, c_float, c_float, c_int, c_float, c_int, c_void_p]),
+    "mcvc_pack_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "mcvc_draw_batch": (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_int, c_longlong, c_int, c_int, c_int,
                                 ctypes.c_ulonglong, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mcvc_audio_frames": (c_int, [c_int]),
