@@ -392,6 +392,30 @@ long long mcvc_gl_workspace_floats(int B, int T);
 int mcvc_gl_decode(const float* in, int in_kind, const float* angles0, const float* tables, float* out, float* workspace,
                    long long workspace_floats, int B, int T, int n_iter, float momentum, void* stream);
 
+/* ---- mel inversion by non-negative least squares (new): log-mel [B][80][T] -> linear magnitude [B][513][T], what mcvc_gl_decode takes
+ *      as in_kind 1 (csrc/melinv_kernels.hip; mask_cyclegan_vc/melinv.py and INTEGRATION.md restate this).  With y = 10^logmel, Bm the
+ *      [80][513] mel basis, P its pseudo-inverse, s = 1 / lambda, lambda the largest eigenvalue of Bm Bm^T, and beta_k = (t_k - 1) / t_k+1,
+ *      t_0 = 1, t_k+1 = (1 + sqrt(1 + 4 t_k^2)) / 2 (float64 on the host, rounded once to fp32), per frame:
+ *        M_0 = max(0, P y), the decoder's own start value bit for bit (exp10f, one fmaf chain over filters 0..79 from zero); Z_0 = M_0;
+ *        for k < n_iter:  r = Bm Z_k - y;  M_k+1 = max(0, Z_k - s Bm^T r);  Z_k+1 = M_k+1 + beta_k (M_k+1 - M_k);   the result is M_n_iter.
+ *      No restart, no stopping test: the problem is underdetermined, the result is defined by this iteration.  Every sum is one fmaf chain
+ *      over ascending bins from zero; no atomics: a frame's result does not depend on its batch, its position or T.  One launch.
+ *        mcvc_melinv_max_iter       the largest n_iter (512).
+ *        mcvc_melinv_tables_floats  size of the constant operand.
+ *        mcvc_melinv_tables_init    HOST -> HOST.  host_basis [80][513] and host_pinv [513][80] fp32; lambda as above.  The kernel uses the
+ *                                   basis through sparse tables (per bin: first filter and two weights; per filter: first bin and count), so
+ *                                   MCVC_ERR_INVALID for a basis with a column of more than two non-zeros, with two that are not in adjacent
+ *                                   filters, with a filter whose non-zeros are not contiguous bins, or with a value that is not finite; also
+ *                                   for a null pointer or a lambda that is not positive and finite.  A refused call writes nothing.  The
+ *                                   caller uploads the result (16-byte aligned) once per device.
+ *        mcvc_melinv_solve          asynchronous on `stream`; no device allocation, no workspace.  MCVC_ERR_INVALID: a null or misaligned
+ *                                   pointer (logmel, mag_out: 4 bytes; tables: 16), B < 1, T < 1, B > 65535, T > 2^20, B T > 2^22, n_iter
+ *                                   outside [0, 512] -- nothing is launched.                                                          */
+int mcvc_melinv_max_iter(void);
+long long mcvc_melinv_tables_floats(void);
+int mcvc_melinv_tables_init(const float* host_basis, const float* host_pinv, double lambda, float* host_out);
+int mcvc_melinv_solve(const float* logmel, const float* tables, float* mag_out, int B, int T, int n_iter, void* stream);
+
 /* ---- objective evaluation (new): mel-cepstra from log-mels and batched dynamic time warping (csrc/dtw_kernels.hip; the definitions are in
  *      mask_cyclegan_vc/metrics.py and INTEGRATION.md).  A feature bank is [K][N] fp32, time-contiguous per row: utterances back to back
  *      along time with an offset table offs[n + 1]; pair p aligns utterance p of bank x with utterance p of bank y.

@@ -22,13 +22,23 @@ class CycleGANTestArgParser(BaseArgParser):
         ("--griffin_lim", dict(type=int, default=0, metavar="N_ITER", help="(new) decode converted and original utterances to 32-bit float .wav files under "
                                "converted_audio/ by N_ITER iterations of Griffin-Lim phase reconstruction on the GPU (mask_cyclegan_vc/griffinlim.py): "
                                "needs no vocoder weights.  0 (default): off.  Not together with --vocoder_ckpt.")),
+        ("--gl_mel_inverse", dict(type=str, choices=("pinv", "nnls"), default=None, help="(new) with --griffin_lim: how the 80 mel bands become the 513-bin "
+                                  "magnitude the phase loop works on.  pinv (default): the clamped pseudo-inverse.  nnls: non-negative least squares on "
+                                  "the GPU (mask_cyclegan_vc/melinv.py), a magnitude whose own mel-spectrogram is the one asked for.")),
+        ("--gl_mel_iter", dict(type=int, default=None, metavar="N", help="(new) with --griffin_lim: iterations of the nnls solver, 0 .. 512 (default 64).")),
         ("--max_batch", dict(type=int, default=16, help="(new) utterances of identical length are converted in one batched forward of up to this many.")),
     ]
 
     def parse_args(self, argv=None):
+        self.parser.set_defaults(gl_mel_inverse=None, gl_mel_iter=None)    # None: the flag was not given
         pre = self.parser.parse_args(argv)                             # refused before any run directory is created
         if pre.griffin_lim < 0:
             self.parser.error("--griffin_lim takes a number of iterations >= 0")
         if pre.griffin_lim and pre.vocoder_ckpt:
             self.parser.error("--griffin_lim and --vocoder_ckpt are two decoders for the same files: give one of them")
+        if (pre.gl_mel_inverse is not None or pre.gl_mel_iter is not None) and not pre.griffin_lim:
+            self.parser.error("--gl_mel_inverse and --gl_mel_iter belong to the Griffin-Lim decoder: give --griffin_lim N_ITER too")
+        if pre.gl_mel_iter is not None and not 0 <= pre.gl_mel_iter <= 512:
+            self.parser.error("--gl_mel_iter takes a number of iterations in [0, 512]")
+        self.parser.set_defaults(gl_mel_inverse="pinv", gl_mel_iter=64)
         return super(CycleGANTestArgParser, self).parse_args(argv)

@@ -26,6 +26,7 @@
 #include "audio.h"
 #include "vocoder.h"
 #include "griffinlim.h"
+#include "melinv.h"
 #include "dtw.h"
 #include "ms.h"
 #include "f0.h"
@@ -2517,6 +2518,22 @@ int mcvc_gl_decode(const float* in, int in_kind, const float* angles0, const flo
                    long long workspace_floats, int B, int T, int n_iter, float momentum, void* stream)
 {
     return mcvc_gl_decode_launch(in, in_kind, angles0, tables, out, workspace, workspace_floats, B, T, n_iter, momentum, (hipStream_t)stream);
+}
+
+// ---- mel inversion by non-negative least squares (melinv_kernels.hip) ----
+int mcvc_melinv_max_iter(void) { return MCVC_MELINV_MAX_ITER; }
+
+long long mcvc_melinv_tables_floats(void) { return mcvc_melinv_tables_floats_of(); }
+
+int mcvc_melinv_tables_init(const float* host_basis, const float* host_pinv, double lambda, float* host_out)
+{
+    if (!host_basis || !host_pinv || !host_out || (((uintptr_t)host_basis | (uintptr_t)host_pinv | (uintptr_t)host_out) & 3)) return MCVC_ERR_INVALID;
+    return mcvc_melinv_tables_fill(host_basis, host_pinv, lambda, host_out);
+}
+
+int mcvc_melinv_solve(const float* logmel, const float* tables, float* mag_out, int B, int T, int n_iter, void* stream)
+{
+    return mcvc_melinv_solve_launch(logmel, tables, mag_out, B, T, n_iter, (hipStream_t)stream);
 }
 
 // ---- objective evaluation: mel-cepstra and batched DTW (dtw_kernels.hip) ----

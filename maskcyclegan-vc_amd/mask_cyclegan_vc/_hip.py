@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_float, c_int, c_longlong, c_void_p
+from ctypes import c_double, c_float, c_int, c_longlong, c_void_p
 
 import torch  # noqa: F401  (must be imported first so libamdhip64.so.7 is already resident)
 
@@ -115,6 +115,10 @@ _SIGS = {
     "mcvc_gl_tables_init": (c_int, [c_void_p, c_void_p]),
     "mcvc_gl_workspace_floats": (c_longlong, [c_int, c_int]),
     "mcvc_gl_decode": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_float, c_void_p]),
+    "mcvc_melinv_max_iter": (c_int, []),
+    "mcvc_melinv_tables_floats": (c_longlong, []),
+    "mcvc_melinv_tables_init": (c_int, [c_void_p, c_void_p, c_double, c_void_p]),
+    "mcvc_melinv_solve": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mcvc_dtw_max_frames": (c_int, []),
     "mcvc_dtw_launches": (c_int, [c_int]),
     "mcvc_cep_basis_init": (c_int, [c_int, c_void_p]),

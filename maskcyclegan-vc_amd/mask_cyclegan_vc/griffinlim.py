@@ -4,6 +4,9 @@ weights -- the audio path for a machine that has no MelGAN checkpoint.
 * ``gl.inverse(mel)``         [B, 80, T] log10-mel -> [B, 256 T] float32 waveform (csrc/griffinlim_kernels.hip through ``mcvc_gl_decode``);
 * ``gl.from_magnitude(mag)``  the same from a linear magnitude [B, 513, T] (non-negative);
 * ``gl(audio)``               waveform -> log-mel, ``data_preprocessing.audio2mel.Audio2Mel``.
+* ``GriffinLimVocoder(mel_inverse="nnls", mel_iter=64)``: ``inverse(mel)`` is ``from_magnitude(MelInverter(n_iter=mel_iter)(mel))`` -- the
+  magnitude comes from the non-negative least-squares solver of ``mask_cyclegan_vc/melinv.py`` instead of the clamped pseudo-inverse
+  below.  The default ``"pinv"`` changes nothing.
 
 The transform is fixed by the front-end's STFT (reflect-pad 384, frames of 1024 at hop 256, periodic Hann w, bins 0..512):
 
@@ -51,10 +54,10 @@ def host_tables():
 
 
 class GriffinLimVocoder(object):
-    """``GriffinLimVocoder(device=None, n_iter=32, momentum=0.99, seed=0)``; then ``inverse(mel)``, ``from_magnitude(mag)`` and
-    ``__call__(audio)``."""
+    """``GriffinLimVocoder(device=None, n_iter=32, momentum=0.99, seed=0, mel_inverse="pinv", mel_iter=64)``; then ``inverse(mel)``,
+    ``from_magnitude(mag)`` and ``__call__(audio)``."""
 
-    def __init__(self, device=None, n_iter=32, momentum=0.99, seed=0):
+    def __init__(self, device=None, n_iter=32, momentum=0.99, seed=0, mel_inverse="pinv", mel_iter=64):
         self.device = _hip.hip_device("mask_cyclegan_vc.griffinlim", device)
         if int(n_iter) < 0:
             raise ValueError("n_iter must be >= 0, got %r" % (n_iter,))
@@ -62,6 +65,12 @@ class GriffinLimVocoder(object):
             raise ValueError("momentum must lie in [0, 1), got %r" % (momentum,))
         self.n_iter, self.momentum, self.seed = int(n_iter), float(momentum), int(seed)
         self._fft = None
+        if mel_inverse not in ("pinv", "nnls"):
+            raise ValueError("mel_inverse is 'pinv' or 'nnls', got %r" % (mel_inverse,))
+        self.mel_inverse, self._melinv = mel_inverse, None
+        if mel_inverse == "nnls":
+            from .melinv import MelInverter
+            self._melinv = MelInverter(self.device, n_iter=mel_iter)
 
     def tables(self):
         return _hip.device_constant("griffinlim.tables", self.device, host_tables)
@@ -112,6 +121,8 @@ class GriffinLimVocoder(object):
 
     def inverse(self, mel, angles=None, n_iter=None, momentum=None):
         """[B, 80, T] log10-mel on the HIP device -> [B, 256 T] float32 waveform; one batched decode on the current stream."""
+        if self._melinv is not None:
+            return self.from_magnitude(self._melinv(mel), angles, n_iter, momentum)
         return self._decode(mel, KIND_LOGMEL, N_MEL, angles, n_iter, momentum)
 
     def from_magnitude(self, mag, angles=None, n_iter=None, momentum=None):

@@ -18,6 +18,9 @@ selects the bf16-MFMA forward (BASELINE configs[4]).
 ``--griffin_lim N_ITER`` (new): the same two files per utterance without any vocoder weights -- N_ITER iterations of Griffin-Lim phase
 reconstruction against the front-end's own STFT (mask_cyclegan_vc/griffinlim.py, csrc/griffinlim_kernels.hip), through the same
 ``write_audio`` path.  Not together with ``--vocoder_ckpt``; with neither flag no audio is written and neither decoder is imported.
+``--gl_mel_inverse nnls`` (new, with ``--griffin_lim`` only; ``--gl_mel_iter N``, default 64): the magnitude the phase loop works on
+comes from the non-negative least-squares solver of mask_cyclegan_vc/melinv.py instead of the clamped pseudo-inverse; the default
+``pinv`` writes the files it always wrote.
 
 ``--wav_dir`` (new): the utterances to convert are the .wav files of a folder instead of the source speaker's pickle; their
 mel-spectrograms come from the GPU front-end (data_preprocessing/audio2mel.py)."""
@@ -55,7 +58,8 @@ class MaskCycleGANVCTesting(object):
             self.vocoder = MelVocoder.from_checkpoint(args.vocoder_ckpt, self.device)
         elif getattr(args, "griffin_lim", 0) > 0:
             from .griffinlim import GriffinLimVocoder
-            self.vocoder = GriffinLimVocoder(self.device, n_iter=args.griffin_lim)
+            self.vocoder = GriffinLimVocoder(self.device, n_iter=args.griffin_lim, mel_inverse=getattr(args, "gl_mel_inverse", "pinv"),
+                                             mel_iter=getattr(args, "gl_mel_iter", 64))
         if self.vocoder is not None:
             self.converted_audio_dir = os.path.join(args.save_dir, args.name, "converted_audio")
             os.makedirs(self.converted_audio_dir, exist_ok=True)
