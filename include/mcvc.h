@@ -31,7 +31,9 @@ extern "C" {
 #endif
 
 #define MCVC_ABI_VERSION 3          /* r4: + mcvc_gen_backward_prefix, mcvc_set_trunk_passes_in_flight, op-level Winograd / staged-GEMM / trunk entries;
-                                       3: + mcvc_gen_update_ranges / mcvc_disc_update_batch (optimizer step fused with the re-pack) */
+                                       3: + mcvc_gen_update_ranges / mcvc_disc_update_batch (optimizer step fused with the re-pack).
+                                       Stays 3 where symbols, flag bits or argument values are only ADDED and every existing call keeps its
+                                       meaning (MCVC_BWD_STORE_GRADS, mcvc_disc_backward_flags, mcvc_grad_store_mask, zero_grads == 2) */
 #define MCVC_GEN_NPARAMS 110
 #define MCVC_DISC_NPARAMS 20
 #define MCVC_N_MEL 80
@@ -157,6 +159,20 @@ int mcvc_debug_trunk_fault_inject(int on);
  *      finishes it, so that the optimizer step of all but conv1 (mcvc_gen_update_ranges, range_mask bits 8 / 16 / 32 = [12,24) / [4,12) /
  *      [0,4); bit 4 = their union, not to be combined with them) runs beside the rest of the pass instead of behind it.                */
 #define MCVC_BWD_FINE_MILESTONES 2
+/*      flags & MCVC_BWD_STORE_GRADS: on return every COVERED parameter gradient (mcvc_grad_store_mask: the weight tensors of the Winograd
+ *      layers, the implicit-GEMM layers and the wide 1 x KW convolutions of the 1-D trunk -- more than 99 % of the parameters) EQUALS this
+ *      pass's gradient, whatever the buffer held before: its writers store instead of reading the old value and adding to it.  The
+ *      uncovered gradients (biases, norm affine parameters, the edge layers) are accumulated into, as without the flag.  Where the writer
+ *      the planner picks for a covered layer can only add (an odd frame count, a missing workspace), the tensor is zero-filled first: the
+ *      contract holds for every shape.  The first weight-gradient pass after an update with zero_grads == 2 passes it; later passes of the
+ *      iteration do not.  The op-level entries (mcvc_conv2d_wgrad, mcvc_layer_*) accumulate; mcvc_layer_wgrad_flags alone takes this flag,
+ *      so that one layer's store mode -- a pass in several sample chunks -- can be driven without a whole network.                      */
+#define MCVC_BWD_STORE_GRADS 4
+/*      covered[p] = 1 for the parameter tensors of network `net` (0 generator, 1 discriminator) that a store pass covers, else 0; 128 bytes
+ *      are written.  Host only, no device call; a property of the layers alone: the mask is the same for every T >= 1 (the argument
+ *      is checked and otherwise unused -- which WRITER a covered layer gets depends on T, whether it is covered does not).  Returns
+ *      the network's parameter count (MCVC_GEN_NPARAMS / MCVC_DISC_NPARAMS), or MCVC_ERR_INVALID.                                       */
+int mcvc_grad_store_mask(int net, int T, unsigned char* covered);
 int mcvc_gen_backward_flags(const float* const* params, const float* packed, float* const* grads, const float* mask,
                             const float* dout, float* dx, int accumulate_dx, const float* stash,
                             float* scratch, long long scratch_floats, int B, int T, void* stream, void* aux_stream,
@@ -243,6 +259,11 @@ int mcvc_disc_backward(const float* const* params, const float* packed, float* c
                        const float* dout, int dout_is_logit_grad, float* dx, int accumulate_dx,
                        const float* stash, float* scratch, long long scratch_floats, int B, int T, void* stream,
                        void* aux_stream);
+/*      ... with flags: MCVC_BWD_STORE_GRADS as for the generator (any other bit: MCVC_ERR_INVALID); flags = 0 is mcvc_disc_backward.     */
+int mcvc_disc_backward_flags(const float* const* params, const float* packed, float* const* grads,
+                             const float* dout, int dout_is_logit_grad, float* dx, int accumulate_dx,
+                             const float* stash, float* scratch, long long scratch_floats, int B, int T, void* stream,
+                             void* aux_stream, int flags);
 
 /* ---- losses (train.py:219-237, 276-294). loss_slot/term_slot: device floats, accumulated (+=) -- */
 /* loss_slot += weight*mean|a-b|, term_slot += mean|a-b|, grad_a (=|+=) weight*sign(a-b)/n           */
@@ -274,7 +295,11 @@ int mcvc_adam_step2(float* p, float* g, float* g2, int zero_grads, float* exp_av
  *      pass over the OIHW tensors: the per-step `pack` kernel family is gone (it remains for load_state_dict: mcvc_*_pack*).
  *      numel[i]: elements of parameter tensor i (0: a parameter that is neither updated nor packed -- the unused downSample4 block);
  *      flat / grad / grad2 (nullable) / exp_avg / exp_avg_sq: flat buffers in which params[i], its gradient(s) and moments sit at EQUAL
- *      offsets (gradient of params[i] = grad + (params[i] - flat)); range_mask / max_batch / T as mcvc_gen_pack_ranges / mcvc_disc_pack_batch. */
+ *      offsets (gradient of params[i] = grad + (params[i] - flat)); range_mask / max_batch / T as mcvc_gen_pack_ranges / mcvc_disc_pack_batch.
+ *      zero_grads: 0 leave the gradients, 1 clear them behind the read, 2 clear only the tensors a store pass does not cover
+ *      (mcvc_grad_store_mask) and leave the covered ones as they are -- the next pass over the network passes MCVC_BWD_STORE_GRADS and never
+ *      reads them, so neither the zeros' store nor their load happens (28 instead of 32 bytes per covered parameter).  2 needs grad2 == NULL;
+ *      any other value, or 2 with a grad2: MCVC_ERR_INVALID.                                                                            */
 int mcvc_gen_update_ranges(const float* const* params, const long long* numel, float* packed, int max_batch, int T, int range_mask,
                            const float* flat, float* grad, float* grad2, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                            float beta2, float eps, int step, float grad_scale, int zero_grads, void* stream);
@@ -554,6 +579,11 @@ int mcvc_layer_dgrad(const float* dy, const float* packed, const float* w0, cons
                      int pad_h, int pad_w, int scheme, void* stream);
 int mcvc_layer_wgrad(const float* x, const float* dy, float* dw0, float* dw1, float* scratch, long long scratch_floats, int N, int H,
                      int W, int Cin, int Cout, int branches, int KH, int KW, int stride, int pad_h, int pad_w, int scheme, void* stream);
+/*      ... with flags = MCVC_BWD_STORE_GRADS: the planner's store mode on this one layer (a layer mcvc_grad_store_mask covers: dw = the
+ *      gradient, whatever dw held; any other layer: dw += as above).  flags = 0 is mcvc_layer_wgrad; other bits: MCVC_ERR_INVALID.       */
+int mcvc_layer_wgrad_flags(const float* x, const float* dy, float* dw0, float* dw1, float* scratch, long long scratch_floats, int N, int H,
+                           int W, int Cin, int Cout, int branches, int KH, int KW, int stride, int pad_h, int pad_w, int scheme, int flags,
+                           void* stream);
 /*      The fused backward of one 1-D trunk layer (SURVEY.md section 8b resblock1d_bwd / gemm1x1_in_bwd; reference model.py:47-76 under
  *      autograd): InstanceNorm (+ gated GLU when the gate pointers are given) backward of dy [Cout][B][T4] recomputed inside the
  *      transposed-convolution launch; dconv [Cx][B][T4] = gradient w.r.t. the conv output (Cx = Cout or 2*Cout, value rows first);

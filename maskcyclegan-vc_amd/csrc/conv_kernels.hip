@@ -797,6 +797,7 @@ struct SmallKArgs {
     long long x_sb, x_sc, dy_sb, dy_sc;
     int x_sh, dy_sh;
     int NB, Cin, Cout, OH, OW, pw;
+    int store;                                        // 1: dW = this pass's gradient (the old values are not read)
 };
 
 // (r3: a thread owns ONE (ci, kw) element of COB consecutive dW rows instead of one ci with its KW taps: the dW read-modify-write -- the
@@ -860,6 +861,12 @@ __global__ void __launch_bounds__(256) wgrad_smallk_kernel(const Twin<SmallKArgs
 #pragma unroll
             for (int c = 0; c < COB; ++c) acc[c] += dr[c * npix + ow] * xv;
         }
+    }
+    if (a.store) {                                    // (uniform: a launch argument)
+#pragma unroll
+        for (int c = 0; c < COB; ++c)
+            if (co0 + c < a.Cout) a.dw[(long long)(co0 + c) * a.Cin * KW + e] = acc[c];
+        return;
     }
     // read-modify-write of the COB rows: all loads first (written as `*d += acc` the compiler keeps the rows' round trips in sequence:
     // it cannot prove that the stores do not alias the next row's load)
@@ -934,6 +941,12 @@ __global__ void __launch_bounds__(256) wgrad_smallk_batch_kernel(const Twin<Smal
             for (int c = 0; c < COB; ++c) acc[c] += dr[c * npix + ow] * xv;
         }
     }
+    if (jb.store) {                                   // (uniform per workgroup: the job's flag)
+#pragma unroll
+        for (int c = 0; c < COB; ++c)
+            if (co0 + c < jb.Cout) jb.dw[(long long)(co0 + c) * jb.Cin * KW + e] = acc[c];
+        return;
+    }
     float old[COB];                                   // (all loads of the read-modify-write first: see wgrad_smallk_kernel)
 #pragma unroll
     for (int c = 0; c < COB; ++c) old[c] = (co0 + c < jb.Cout) ? jb.dw[(long long)(co0 + c) * jb.Cin * KW + e] : 0.f;
@@ -956,7 +969,7 @@ int mcvc_wgrad_smallk_batch_launch(const SmallKJob* jobs, int njobs, int B, int 
         bt.first[j] = total;
         total += cdiv_i(jobs[j].Cout, kSmallKBatchCob) * cdiv_i(jobs[j].Cin * 3, 256);
         flops += 2.0 * px * jobs[j].Cout * jobs[j].Cin * 3;
-        bytes += 4.0 * (2.0 * jobs[j].Cout * jobs[j].Cin * 3 + px * (jobs[j].Cin + jobs[j].Cout));
+        bytes += 4.0 * ((jobs[j].store ? 1.0 : 2.0) * jobs[j].Cout * jobs[j].Cin * 3 + px * (jobs[j].Cin + jobs[j].Cout));
     }
     bt.first[njobs] = total; bt.njobs = njobs; bt.B = B; bt.T4 = T4;
     TraceScope ts(K_WGRAD_SMALLK, s, flops, bytes);
@@ -1113,6 +1126,7 @@ static bool plan_wgrad(const ConvProblem& p, int NB, long long slab_cap_floats, 
 }  // namespace
 
 static bool smallk_applies(const ConvProblem& p, int NB);
+bool mcvc_wgrad_smallk_applies(const ConvProblem& p, int NB) { return smallk_applies(p, NB); }
 long long mcvc_wgrad_plan_slab_floats(const ConvProblem& p, int NB)
 {
     if (smallk_applies(p, NB)) return 0;
@@ -1132,20 +1146,21 @@ static bool smallk_applies(const ConvProblem& p, int NB)
     return p.KH == 1 && p.stride == 1 && (p.KW == 1 || p.KW == 3) && p.pad_h == 0 && (long long)NB * p.OH * p.OW <= 128 && p.OW == p.W;
 }
 
-int mcvc_wgrad_launch(const ConvProblem& p, int NB, const WgradIO& io, float* dw, float* slabs, long long slab_cap_floats, hipStream_t s)
+int mcvc_wgrad_launch(const ConvProblem& p, int NB, const WgradIO& io, float* dw, float* slabs, long long slab_cap_floats, hipStream_t s, int store)
 {
+    if (store && !smallk_applies(p, NB)) return MCVC_ERR_INVALID;       // (the slab / atomic kernels below only add)
     if (smallk_applies(p, NB)) {
         SmallKArgs k{};
         k.x = io.x; k.dy = io.dy; k.dw = dw;
         k.x_sb = io.x_sb; k.x_sc = io.x_sc; k.x_sh = io.x_sh;
         k.dy_sb = io.dy_sb; k.dy_sc = io.dy_sc; k.dy_sh = io.dy_sh;
-        k.NB = NB; k.Cin = p.Cin; k.Cout = p.Cout; k.OH = p.OH; k.OW = p.OW; k.pw = p.pad_w;
+        k.NB = NB; k.Cin = p.Cin; k.Cout = p.Cout; k.OH = p.OH; k.OW = p.OW; k.pw = p.pad_w; k.store = store ? 1 : 0;
         // output channels per workgroup: every workgroup stages the x rows of its 256 (ci, kw) elements, so layers with enough workgroups
         // (conv1dto2d 5120 x 256, conv2dto1d 256 x 5120) take 16 rows per workgroup instead of 4 (a quarter of the x re-reads)
         const int COB = (p.KW == 1 && cdiv_i(p.Cout, 16) * cdiv_i(p.Cin, 256) >= 256) ? 16 : 4;
         dim3 grid((unsigned)cdiv_i(p.Cout, COB), (unsigned)cdiv_i(p.Cin * p.KW, 256));
         const double px = (double)NB * p.OH * p.OW;
-        TraceScope ts(K_WGRAD_SMALLK, s, 2.0 * px * p.Cout * p.Cin * p.KW, 4.0 * (2.0 * p.Cout * p.Cin * p.KW + px * (p.Cin + p.Cout)));
+        TraceScope ts(K_WGRAD_SMALLK, s, 2.0 * px * p.Cout * p.Cin * p.KW, 4.0 * ((store ? 1.0 : 2.0) * p.Cout * p.Cin * p.KW + px * (p.Cin + p.Cout)));
         const int npix = NB * p.OH * p.OW;
         const size_t lds = (size_t)(COB * npix + (256 / p.KW + 2) * (npix + 1)) * sizeof(float);       // <= 64 KB at 128 pixels
         if (p.KW == 3) mcvc_launch((wgrad_smallk_kernel<3, 4>), grid, dim3(256), lds, s, k);

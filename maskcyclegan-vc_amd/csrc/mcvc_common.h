@@ -213,7 +213,9 @@ struct WgradIO {
     const float* x; long long x_sb, x_sc; int x_sh;
     const float* dy; long long dy_sb, dy_sc; int dy_sh;
 };
-int mcvc_wgrad_launch(const ConvProblem& p, int NB, const WgradIO& io, float* dw, float* slabs, long long slab_cap_floats, hipStream_t s);
+// `store` (only where mcvc_wgrad_smallk_applies: the small-K kernel): dw = this call's gradient instead of dw += it; else MCVC_ERR_INVALID
+int mcvc_wgrad_launch(const ConvProblem& p, int NB, const WgradIO& io, float* dw, float* slabs, long long slab_cap_floats, hipStream_t s, int store = 0);
+bool mcvc_wgrad_smallk_applies(const ConvProblem& p, int NB);
 // conv1's weight gradient (Cin <= 2, 5 x 15) on the matrix cores (fewout_kernels.hip); dw accumulates
 bool mcvc_wgrad_cin2_applies(const ConvProblem& p, const WgradIO& io);
 int mcvc_wgrad_cin2_launch(const ConvProblem& p, int NB, const WgradIO& io, float* dw, hipStream_t s);
@@ -226,9 +228,12 @@ int mcvc_wgrad_cout1_launch(const ConvProblem& p, int NB, const WgradIO& io, flo
 // scratch floats the K-split of this weight gradient wants (0 = no split)
 long long mcvc_wgrad_plan_slab_floats(const ConvProblem& p, int NB);
 
+// p[0..n) = 0.f as a kernel launch (trunk_kernels.hip zero_words_kernel): a gradient tensor in front of a writer that can only add
+int mcvc_zero_words_launch(float* p, long long n, hipStream_t s);
+
 // Batched small-K weight gradients (1-D trunk at small batch): all of a backward pass's trunk layers in ONE launch.
 // Every job is dW[co][ci][kw] += sum_{b,t} dY[co][b][t] * X[ci][b][t + kw - 1]  with dY, X in trunk layout [C][B][T4].
-struct SmallKJob { const float* x; const float* dy; float* dw; int Cin, Cout; int xB; };   // xB: samples per channel of x (0 = B)
+struct SmallKJob { const float* x; const float* dy; float* dw; int Cin, Cout; int xB; int store; };   // xB: samples per channel of x (0 = B); store: dW = ..., not +=
 #define MCVC_SMALLK_MAX_JOBS 24
 int mcvc_wgrad_smallk_batch_launch(const SmallKJob* jobs, int njobs, int B, int T4, hipStream_t s);
 bool mcvc_wgrad_smallk_batch_applies(int B, int T4);

@@ -83,6 +83,7 @@ struct Exec {
     int y_xs_pw = 0; long long y_xs_plane = 0;   // the next norm_fwd writes y in the phase-split padded layout (sgemm.h); consumed by norm_fwd
     int dx_pitch = 0;              // the next norm_bwd writes dx in the padded dY layout (rows of dx_pitch floats + a zero row); consumed by norm_bwd
     int wgrad_x_xs = 0;            // conv_wgrad: x is in the phase-split padded layout
+    int store_grads = 0;           // backward pass: the weight gradients of the covered layers are STORED (MCVC_BWD_STORE_GRADS; conv_wgrad)
     int force_scheme = 0;          // op-level entries (mcvc_layer_*): 0 planner's choice, 1 Winograd with 2x2 output tiles only, 2 with 4x4 tiles
                                    // (thresholds on samples / tiles lifted), 3 no Winograd, 4 no Winograd and no staged GEMM (direct kernels)
     PackFresh fresh;               // per layer, the forms the last re-pack of `packed` left fresh (never packed through a restricted entry: all)
@@ -286,7 +287,7 @@ struct WinoFam {
     int (*input_t)(const WinoXformArgs&, hipStream_t);                          // the weight gradient's tile-major operands ...
     int (*input_phase_t)(const WinoXformArgs&, int XH, int XW, hipStream_t);
     int (*dy_t)(const WinoXformArgs&, hipStream_t);
-    int (*dw)(const float* du, float* dw0, float* dw1, int Cout, int nbr, int Cin, hipStream_t);      // ... and dW += G^T dU G
+    int (*dw)(const float* du, float* dw0, float* dw1, int Cout, int nbr, int Cin, int store, hipStream_t);      // ... and dW (+)= G^T dU G
 };
 enum { kF23, kF25, kF43, kF45 };          // F(2x2,3x3), F(2x2,5x5), F(4x4,3x3), F(4x4,5x5)
 static const WinoFam kWino[4] = {
@@ -294,12 +295,12 @@ static const WinoFam kWino[4] = {
      nullptr, mcvc_wino3_input_phase_t_launch, mcvc_wino3_dy_t_launch, mcvc_wino3_dw_launch},
     {36, 0, 2, 2, 32, 36, mcvc_wino_input_launch, nullptr, mcvc_wino_output_launch,
      mcvc_wino_input_t_launch, nullptr, mcvc_wino_dy_t_launch,
-     [](const float* du, float* dw0, float*, int Cout, int, int Cin, hipStream_t s) { return mcvc_wino_dw_launch(du, dw0, Cout, Cin, s); }},
+     [](const float* du, float* dw0, float*, int Cout, int, int Cin, int store, hipStream_t s) { return mcvc_wino_dw_launch(du, dw0, Cout, Cin, store, s); }},
     {36, 36, 4, 1, 32, 43, mcvc_wino43_input_launch, mcvc_wino43_input_phase_launch, mcvc_wino43_output_launch,
      nullptr, mcvc_wino43_input_phase_t_launch, mcvc_wino43_dy_t_launch, mcvc_wino43_dw_launch},
     {64, 64, 4, 2, 64 /* (the GEMM wants a pitch of 64+ columns) */, 64, mcvc_wino4_input_launch, nullptr, mcvc_wino4_output_launch,
      mcvc_wino4_input_t_launch, nullptr, mcvc_wino4_dy_t_launch,
-     [](const float* du, float* dw0, float*, int Cout, int, int Cin, hipStream_t s) { return mcvc_wino4_dw_launch(du, dw0, Cout, Cin, s); }},
+     [](const float* du, float* dw0, float*, int Cout, int, int Cin, int store, hipStream_t s) { return mcvc_wino4_dw_launch(du, dw0, Cout, Cin, store, s); }},
 };
 static long long wino_tiles(const WinoFam& f, int H, int W) { return (long long)((H + f.tile - 1) / f.tile) * ((W + f.tile - 1) / f.tile); }
 
@@ -372,11 +373,12 @@ static void wino_pass(Exec& ex, const WinoPass& p, CView x, View y)
 }
 
 // One weight-gradient pass on stream ws, in chunks of nbc samples: the tile-major operands Vt[xi][tile][ci] from x and dMt[xi][tile][co] = A dY A^T,
-// f.pts products dU[xi] = dMt[xi]^T Vt[xi] over the tiles, then dW += G^T dU G -- the chunks add up in dw.  A stride-2 layer runs in the phase
+// f.pts products dU[xi] = dMt[xi]^T Vt[xi] over the tiles, then dW += G^T dU G -- the chunks add up in dw (`store`: the FIRST chunk stores its
+// gradient instead of adding to what dw held, the later ones add to it).  A stride-2 layer runs in the phase
 // formulation (see conv_wino3): dU[xi][co][4ci+2p+q], both branches (value | gate) in one product, the 3x3 blocks scattered back into the two
 // 5x5 gradients.
 static void wino_wgrad_pass(Exec& ex, const WinoFam& f, const ConvSpec& c, float* const* grads, int NB, int nbc, int H, int W, CView x, CView dy,
-                            hipStream_t ws)
+                            int store, hipStream_t ws)
 {
     const bool phase = c.stride == 2;
     const int IH = phase ? H / 2 : H, IW = phase ? W / 2 : W, N = phase ? 4 * c.Cin : c.Cin, M = c.cout_tot;
@@ -399,7 +401,7 @@ static void wino_wgrad_pass(Exec& ex, const WinoFam& f, const ConvSpec& c, float
         // (rows [NT, NTp) of the tile-major operands are zeros: contract over the 16-row stages that hold tiles -- 80 instead of 96 at one sample)
         ga.M = M; ga.N = N; ga.K = (int)((NT + 15) & ~15LL); ga.nxi = f.nxi;
         ex.fail(mcvc_wino_gemm_launch(ga, ws));
-        ex.fail(f.dw(ex.wu, grads[c.wi[0]], c.nbr == 2 ? grads[c.wi[1]] : nullptr, c.Cout, c.nbr, c.Cin, ws));
+        ex.fail(f.dw(ex.wu, grads[c.wi[0]], c.nbr == 2 ? grads[c.wi[1]] : nullptr, c.Cout, c.nbr, c.Cin, store && b0 == 0, ws));
     }
 }
 
@@ -744,6 +746,10 @@ static int wgrad_cin1_enabled()
     return en;
 }
 
+// Store mode (ex.store_grads, a covered layer: grad_store_covered): on return the layer's weight gradients EQUAL this pass's, whatever the
+// buffer held.  The writers that can store do (the first one of a pass that runs in chunks / slabs; the rest add to it); in front of a
+// writer that can only add -- the direct kernel with slabs or atomics, a fall-back at an odd frame count or without a workspace -- the
+// tensor is zero-filled on the writer's stream.  So correctness never depends on which writer the planner picks, only the speed does.
 static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, int NB, int H, int W, CView x, CView dy)
 {
     const int OH = conv_out(H, c.KH, c.stride, c.ph), OW = conv_out(W, c.KW, c.stride, c.pw);
@@ -785,6 +791,11 @@ static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, int NB,
         ex.fail(mcvc_stream_wait(ex.s2, e));
         ws = ex.s2;
     }
+    const bool store = ex.store_grads && grad_store_covered(c);
+    const long long wnumel = (long long)c.Cout * c.Cin * c.KH * c.KW;
+    auto zero_fill = [&](int br, hipStream_t zs) {            // store mode in front of a writer that can only add
+        if (store && grads[c.wi[br]]) ex.fail(mcvc_zero_words_launch(grads[c.wi[br]], wnumel, zs));
+    };
     bool done = false;
     if (implicit && (wg_split == 1 || (ex.sgw && sg_floats <= ex.sgw_cap)) && grads[c.wi[0]] && (c.nbr == 1 || grads[c.wi[1]])) {
         WGemmArgs g{};
@@ -800,13 +811,13 @@ static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, int NB,
         g.OW = OW; g.P = OH * OW; g.NPIX = NB * g.P;
         g.M = c.cout_tot; g.Cin = c.Cin; g.nsplit = wg_split;
         if (wg_split == 1) {
-            g.c = grads[c.wi[0]]; g.accumulate = 1;
+            g.c = grads[c.wi[0]]; g.accumulate = store ? 0 : 1;
             if (c.nbr == 2) { g.c2 = grads[c.wi[1]]; g.m_split = c.Cout; }
             ex.fail(mcvc_wgemm_launch(g, ws));
         } else {
             g.c = ex.sgw; g.c_split = (long long)c.cout_tot * KT; g.c_slab = ex.sgw + g.c_split;
             ex.fail(mcvc_wgemm_launch(g, ws));
-            ex.fail(mcvc_dw_accum_launch(ex.sgw, wg_split, g.c_split, grads[c.wi[0]], c.nbr == 2 ? grads[c.wi[1]] : nullptr, c.Cout, c.cout_tot, KT, ws));
+            ex.fail(mcvc_dw_accum_launch(ex.sgw, wg_split, g.c_split, grads[c.wi[0]], c.nbr == 2 ? grads[c.wi[1]] : nullptr, c.Cout, c.cout_tot, KT, ws, store));
         }
         done = true;
     }
@@ -818,7 +829,7 @@ static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, int NB,
         auto attempt = [&](const WinoFam& f, int en, int min_tiles) {
             if (!en || (M % 128) != 0 || (N % 64) != 0 || (long long)f.pts * M * N > ex.wu_cap) return false;
             const int nbc = wino_nbc(ex, f, NB, wino_tiles(f, IH, IW), M > N ? M : N, min_tiles);
-            if (nbc) wino_wgrad_pass(ex, f, c, grads, NB, nbc, H, W, x, dy, ws);
+            if (nbc) wino_wgrad_pass(ex, f, c, grads, NB, nbc, H, W, x, dy, store, ws);
             return nbc != 0;
         };
         // (MCVC_WINO_WGRAD switches the 36-point form only)
@@ -827,19 +838,21 @@ static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, int NB,
     }
     if (!done && c.cout_tot == 1 && mcvc_wgrad_cout1_applies(p) && grads[c.wi[0]]) {       // one output channel: VALU kernel
         WgradIO io{x.p, x.sb, x.sc, x.sh, dy.p, dy.sb, dy.sc, dy.sh};
-        ex.fail(mcvc_wgrad_cout1_launch(p, NB, io, grads[c.wi[0]], ws));
+        ex.fail(mcvc_wgrad_cout1_launch(p, NB, io, grads[c.wi[0]], ws));          // (an edge layer: never covered, always adds)
         done = true;
     }
     for (int br = 0; br < c.nbr && !done; ++br) {
         float* dw = grads[c.wi[br]];
         if (!dw) continue;
         WgradIO io{x.p, x.sb, x.sc, x.sh, dy.p + (long long)br * c.Cout * dy.sc, dy.sb, dy.sc, dy.sh};
-        if (mcvc_wgrad_cin1_applies(p) && wgrad_cin1_enabled()) { ex.fail(mcvc_wgrad_cin1_launch(p, NB, io, dw, ws)); continue; }
+        if (mcvc_wgrad_cin1_applies(p) && wgrad_cin1_enabled()) { ex.fail(mcvc_wgrad_cin1_launch(p, NB, io, dw, ws)); continue; }      // (edge layers, like cin2 below)
         // last layer of a backward pass with nothing left for the main stream (conv1 without an input gradient): the gate branch runs
         // there, beside the value branch on the auxiliary stream (atomic accumulation into its own tensor, no slabs to share)
         const bool on_main = br == 1 && ex.br1_on_main && ex.s2 && !mcvc_deterministic() && (long long)c.Cout * c.Cin * c.KH * c.KW <= 65536;
         if (mcvc_wgrad_cin2_applies(p, io)) { ex.fail(mcvc_wgrad_cin2_launch(p, NB, io, dw, on_main ? ex.s : ws)); continue; }
-        ex.fail(mcvc_wgrad_launch(p, NB, io, dw, ex.wslabs, ex.wslab_cap, on_main ? ex.s : ws));
+        const bool sk_store = store && mcvc_wgrad_smallk_applies(p, NB);          // (the small-K kernel stores; the slab / atomic kernels only add)
+        if (!sk_store) zero_fill(br, on_main ? ex.s : ws);
+        ex.fail(mcvc_wgrad_launch(p, NB, io, dw, ex.wslabs, ex.wslab_cap, on_main ? ex.s : ws, sk_store));
     }
     if (ex.s2) {
         hipEvent_t e = pool_event();
@@ -921,11 +934,24 @@ static int pack_net(const DevPackTable* t, const float* const* params, float* pa
 // (biases, norm affine parameters, tensors nothing is packed from) -- so that one launch is optimizer.step() AND the refresh of every
 // copy the kernels read (reference train.py:242,299).
 struct DevUpdTable { UpdOwner* owners; PackJob* jobs; PackDgradArgs* dga; int nown, nblocks; double adam_floats, pack_bytes; std::vector<int> used;
-                     std::vector<long long> sizes; };      // sizes[k]: element count of parameter used[k] the tiles were built for
+                     std::vector<long long> sizes;         // sizes[k]: element count of parameter used[k] the tiles were built for
+                     double covered_floats; };             // ... of which in tensors a zero_grads == 2 update leaves uncleared (UpdOwner::covered)
 
 // host half: the owners and the re-ordered jobs (no device call)
-struct UpdPlan { std::vector<UpdOwner> owners; std::vector<PackJob> jobs; int nblocks = 0; double adam_floats = 0.0; std::vector<int> used; std::vector<long long> sizes; };
-static int plan_upd(const PackTable& t, const long long* numel, int nparams, const std::vector<char>& in_range, UpdPlan& u)
+struct UpdPlan { std::vector<UpdOwner> owners; std::vector<PackJob> jobs; int nblocks = 0; double adam_floats = 0.0, covered_floats = 0.0;
+                 std::vector<int> used; std::vector<long long> sizes; };
+// the weight tensors of a plan's layers whose gradient writers can store (grad_store_covered): indexed by parameter
+static std::vector<char> covered_params(const PackPlan& k, const ConvSpec* const* specs)
+{
+    std::vector<char> cov(128, 0);
+    for (const auto& lf : k.layers) {
+        const ConvSpec& c = *specs[lf.first];
+        if (!grad_store_covered(c)) continue;
+        for (int br = 0; br < c.nbr; ++br) if (c.wi[br] >= 0 && c.wi[br] < 128) cov[c.wi[br]] = 1;
+    }
+    return cov;
+}
+static int plan_upd(const PackTable& t, const long long* numel, int nparams, const std::vector<char>& in_range, const std::vector<char>& covered, UpdPlan& u)
 {
     std::vector<PackJob>& jobs = u.jobs;                  // re-ordered: the emits of one parameter are consecutive
     std::vector<UpdOwner>& owners = u.owners;
@@ -966,7 +992,9 @@ static int plan_upd(const PackTable& t, const long long* numel, int nparams, con
             o.gx = cdiv_i(o.Cin, o.IB);
             nblocks += o.gx * cdiv_i(o.Cout, o.CB);
         }
+        o.covered = (!o.flat && covered[prm]) ? 1 : 0;
         u.adam_floats += (double)numel[prm];
+        if (o.covered) u.covered_floats += (double)numel[prm];
         for (const PackJob& j : mine) jobs.push_back(j);
         owners.push_back(o);
         u.used.push_back(prm); u.sizes.push_back(numel[prm]);
@@ -986,9 +1014,9 @@ static const DevUpdTable* dev_upd_table(PackPlan k, const ConvSpec* const* specs
     if (it != cache.end()) return &it->second;
     PackTable t = build_table(k, specs);
     UpdPlan u;
-    if (int e = plan_upd(t, numel, nparams, in_range, u)) { *err = e; return nullptr; }
+    if (int e = plan_upd(t, numel, nparams, in_range, covered_params(k, specs), u)) { *err = e; return nullptr; }
     DevUpdTable d{};
-    d.adam_floats = u.adam_floats; d.used = u.used; d.sizes = u.sizes;
+    d.adam_floats = u.adam_floats; d.covered_floats = u.covered_floats; d.used = u.used; d.sizes = u.sizes;
     d.nown = (int)u.owners.size(); d.nblocks = u.nblocks;
     d.pack_bytes = t.wbytes;
     if (u.jobs.empty()) u.jobs.push_back(PackJob{});
@@ -1012,6 +1040,7 @@ static int update_net(const DevUpdTable* t, const float* const* params, const lo
 {
     for (size_t k = 0; k < t->used.size(); ++k) if (numel[t->used[k]] != t->sizes[k]) return MCVC_ERR_INVALID;      // (the table is cached per configuration)
     if (!o.flat || !o.grad || !o.exp_avg || !o.exp_avg_sq || o.step < 1) return MCVC_ERR_INVALID;
+    if (o.zero_grads < 0 || o.zero_grads > 2 || (o.zero_grads == 2 && o.grad2)) return MCVC_ERR_INVALID;      // (store mode: one gradient buffer)
     if ((((uintptr_t)o.flat | (uintptr_t)o.grad | (uintptr_t)o.grad2 | (uintptr_t)o.exp_avg | (uintptr_t)o.exp_avg_sq) & 15) != 0) return MCVC_ERR_INVALID;
     PackPtrs ptrs{};
     for (int i : t->used) { if (i < 0 || i >= 128 || !params[i] || (((uintptr_t)params[i]) & 15) != 0) return MCVC_ERR_INVALID; ptrs.p[i] = params[i]; }
@@ -1020,7 +1049,9 @@ static int update_net(const DevUpdTable* t, const float* const* params, const lo
     ad.has_g2 = o.grad2 ? 1 : 0; ad.d_g2 = o.grad2 ? o.grad2 - o.flat : 0;
     ad.zero = o.zero_grads;
     ad.c = mcvc_adam_coef(o.lr, o.beta1, o.beta2, o.eps, o.step, o.grad_scale);
-    const double bytes = (28.0 + (o.grad2 ? 4.0 : 0.0) + (o.zero_grads ? (o.grad2 ? 8.0 : 4.0) : 0.0)) * t->adam_floats + t->pack_bytes;
+    // (zero_grads == 2: 28 B per covered parameter -- its gradient is read and left alone -- and 32 B per uncovered one)
+    const double bytes = o.zero_grads == 2 ? 28.0 * t->adam_floats + 4.0 * (t->adam_floats - t->covered_floats) + t->pack_bytes
+                                           : (28.0 + (o.grad2 ? 4.0 : 0.0) + (o.zero_grads ? (o.grad2 ? 8.0 : 4.0) : 0.0)) * t->adam_floats + t->pack_bytes;
     return mcvc_update_net_launch(t->owners, t->nown, t->nblocks, t->jobs, t->dga, ptrs, packed, ad, bytes, s);
 }
 
@@ -1547,6 +1578,7 @@ static void gen_backward_impl(Exec& ex, const float* const* P, const float* pack
     SmallKJob wjobs[MCVC_SMALLK_MAX_JOBS];
     int nwjobs = 0;
     const bool batch_w = batch_knob && mcvc_wgrad_smallk_batch_applies(B, W4) && (W4 <= 128);
+    auto wstore = [&](const ConvSpec& c) { return (ex.store_grads && grad_store_covered(c)) ? 1 : 0; };      // (the batched launch's per-job flag)
     // Persistent backward (trunk.h): the 12 dependent data-gradient layers of the six blocks in ONE launch, when every layer would take the
     // fused path anyway, the gradient arriving from conv1dto2d is not split into slabs and the staged gradients fit the LDS
     static const int bwd_net_knob = mcvc_knob("MCVC_TRUNK_BWD_NET", 1);
@@ -1573,9 +1605,9 @@ static void gen_backward_impl(Exec& ex, const float* const* P, const float* pack
             db.dg0 = G[b + 2]; db.db0 = G[b + 3]; db.dg1 = G[b + 6]; db.db1 = G[b + 7];
             db.out = DH; db.pre = 2; db.C = 512; db.M = 256; db.rows = 4;
             db.flags = TBWD_ACCUMULATE | TBWD_DY_FRESH | ((i == 5 && ns > 1) ? TBWD_SLAB_OUT : 0);
-            wjobs[nwjobs++] = SmallKJob{st + o.r[i].ya, dt3, G[g.res_out[i].wi[0]], 512, 256, pxB};
-            wjobs[nwjobs++] = SmallKJob{hin, dt1, G[g.res_vg[i].wi[0]], 256, 512, pxB};
-            wjobs[nwjobs++] = SmallKJob{hin, dt1 + 512LL * BT4, G[g.res_vg[i].wi[1]], 256, 512, pxB};
+            wjobs[nwjobs++] = SmallKJob{st + o.r[i].ya, dt3, G[g.res_out[i].wi[0]], 512, 256, pxB, wstore(g.res_out[i])};
+            wjobs[nwjobs++] = SmallKJob{hin, dt1, G[g.res_vg[i].wi[0]], 256, 512, pxB, wstore(g.res_vg[i])};
+            wjobs[nwjobs++] = SmallKJob{hin, dt1 + 512LL * BT4, G[g.res_vg[i].wi[1]], 256, 512, pxB, wstore(g.res_vg[i])};
         }
         na.nlayers = l; na.B = B; na.T4 = W4; na.slabs = ex.slabs; na.slab_stride = 256 * BT4; na.nslab = ns; na.sync = ex.sync + MCVC_TRUNK_SYNC_WORDS; na.err = ex.sync + MCVC_TRUNK_SYNC_WORDS - 1;
         for (int i = 0; i < 6; ++i) { wait_readers(ex, sc + q.dtx3 + (long long)i * 256 * BT4); wait_readers(ex, sc + q.dtx1 + (long long)i * 1024 * BT4); }
@@ -1597,9 +1629,9 @@ static void gen_backward_impl(Exec& ex, const float* const* P, const float* pack
             ns = 1;
             trunk_dgrad(ex, g.res_vg[i], packed, DT2, DH, 1, B, W4, &ns, &pb);
             if (batch_w) {          // weight gradients of the block: queued for the batched launch behind the chain
-                wjobs[nwjobs++] = SmallKJob{st + o.r[i].ya, DT3, G[g.res_out[i].wi[0]], 512, 256, pxB};
-                wjobs[nwjobs++] = SmallKJob{hin, DT1, G[g.res_vg[i].wi[0]], 256, 512, pxB};
-                wjobs[nwjobs++] = SmallKJob{hin, DT1 + 512LL * BT4, G[g.res_vg[i].wi[1]], 256, 512, pxB};
+                wjobs[nwjobs++] = SmallKJob{st + o.r[i].ya, DT3, G[g.res_out[i].wi[0]], 512, 256, pxB, wstore(g.res_out[i])};
+                wjobs[nwjobs++] = SmallKJob{hin, DT1, G[g.res_vg[i].wi[0]], 256, 512, pxB, wstore(g.res_vg[i])};
+                wjobs[nwjobs++] = SmallKJob{hin, DT1 + 512LL * BT4, G[g.res_vg[i].wi[1]], 256, 512, pxB, wstore(g.res_vg[i])};
             } else {
                 conv_wgrad(ex, g.res_out[i], G, 1, B, W4, CView{st + o.r[i].ya, 0, SBT4, W4}, CView{DT3, 0, BT4, W4});
                 conv_wgrad(ex, g.res_vg[i], G, 1, B, W4, CView{hin, 0, SBT4, W4}, CView{DT1, 0, BT4, W4});
@@ -2263,7 +2295,7 @@ int mcvc_pack_plan(int net, int max_batch, int T, int sets, int range_mask, int 
         net_numel(specs, nl, numel);
         std::vector<char> in_range(nparams, 1);
         if (net == 0) for (int p = 0; p < nparams; ++p) in_range[p] = gen_in_range(range_mask, p);
-        if (int e = plan_upd(t, numel, nparams, in_range, u)) return e;
+        if (int e = plan_upd(t, numel, nparams, in_range, covered_params(k, specs), u)) return e;
     }
     const std::vector<PackJob>& jobs = update ? u.jobs : t.jobs;
     PlanRows R{rows, cap};
@@ -2293,6 +2325,22 @@ int mcvc_pack_plan(int net, int max_batch, int T, int sets, int range_mask, int 
     }
     *n_rows = R.n;
     return R.n > cap ? MCVC_ERR_WORKSPACE : 0;
+}
+
+// which parameter tensors a store pass covers (grad_store_covered; host only, no device call): covered[p] = 1 for the weight tensors of
+// the covered layers, 0 for everything else; returns the network's parameter count
+int mcvc_grad_store_mask(int net, int T, unsigned char* covered)
+{
+    if ((net != 0 && net != 1) || T < 1 || !covered) return MCVC_ERR_INVALID;
+    memset(covered, 0, 128);
+    const ConvSpec* const* specs = net == 0 ? gen_specs() : disc_specs();
+    const int nl = net == 0 ? kMaxLayers : 5;
+    for (int l = 0; l < nl; ++l) {
+        const ConvSpec& c = *specs[l];
+        if (!grad_store_covered(c)) continue;
+        for (int br = 0; br < c.nbr; ++br) covered[c.wi[br]] = 1;
+    }
+    return net == 0 ? MCVC_GEN_NPARAMS : MCVC_DISC_NPARAMS;
 }
 
 int mcvc_gen_forward(const float* const* params, const float* packed, const float* x, const float* mask, float* out, float* stash,
@@ -2367,6 +2415,7 @@ int mcvc_gen_backward_window(const float* const* params, const float* packed, fl
         if (!(ex.fresh.layer[l] & spec_forms(*gen_specs()[l]) & side_forms(PACK_SIDE_BWD))) return MCVC_ERR_INVALID;
     ex.no_join = (flags & 1) && aux_stream;
     ex.fine_ms = (flags & 2) != 0;
+    ex.store_grads = (flags & MCVC_BWD_STORE_GRADS) ? 1 : 0;
     gen_backward_impl(ex, params, packed, grads, mask, dout, dx, accumulate_dx, stash, scratch, d, milestones, stash_B, stash_b0);
     return ex.err;
 }
@@ -2397,11 +2446,21 @@ int mcvc_disc_backward(const float* const* params, const float* packed, float* c
                        float* dx, int accumulate_dx, const float* stash, float* scratch, long long scratch_floats, int B, int T, void* stream,
                        void* aux_stream)
 {
+    return mcvc_disc_backward_flags(params, packed, grads, dout, dout_is_logit_grad, dx, accumulate_dx, stash, scratch, scratch_floats, B, T, stream,
+                                    aux_stream, 0);
+}
+
+int mcvc_disc_backward_flags(const float* const* params, const float* packed, float* const* grads, const float* dout, int dout_is_logit_grad,
+                             float* dx, int accumulate_dx, const float* stash, float* scratch, long long scratch_floats, int B, int T, void* stream,
+                             void* aux_stream, int flags)
+{
+    if (flags & ~MCVC_BWD_STORE_GRADS) return MCVC_ERR_INVALID;
     if (B < 1 || T < 1 || !params || !packed || !dout || !stash || !scratch) return MCVC_ERR_INVALID;
     const DiscDims d = disc_dims(B, T);
     Exec ex = make_exec(stream, aux_stream, scratch, scratch_floats, disc_scratch(d).slabs, disc_needs(B, T));
     if (ex.wslab_cap < 0) return MCVC_ERR_WORKSPACE;
     ex.fresh = get_fresh(packed);
+    ex.store_grads = (flags & MCVC_BWD_STORE_GRADS) ? 1 : 0;
     disc_backward_impl(ex, params, packed, grads, dout, dout_is_logit_grad, dx, accumulate_dx, stash, scratch, d);
     return ex.err;
 }
@@ -2878,6 +2937,16 @@ int mcvc_layer_dgrad(const float* dy, const float* packed, const float* w0, cons
 int mcvc_layer_wgrad(const float* x, const float* dy, float* dw0, float* dw1, float* scratch, long long scratch_floats, int N, int H, int W,
                      int Cin, int Cout, int branches, int KH, int KW, int stride, int pad_h, int pad_w, int scheme, void* stream)
 {
+    return mcvc_layer_wgrad_flags(x, dy, dw0, dw1, scratch, scratch_floats, N, H, W, Cin, Cout, branches, KH, KW, stride, pad_h, pad_w, scheme, 0, stream);
+}
+
+// ... with the backward passes' flags: MCVC_BWD_STORE_GRADS runs conv_wgrad in store mode on this ONE layer (a covered layer's gradient is
+// stored, an uncovered one's accumulated into: the planner's rule, reachable per layer for the tests)
+int mcvc_layer_wgrad_flags(const float* x, const float* dy, float* dw0, float* dw1, float* scratch, long long scratch_floats, int N, int H, int W,
+                           int Cin, int Cout, int branches, int KH, int KW, int stride, int pad_h, int pad_w, int scheme, int flags, void* stream)
+{
+    if (flags & ~MCVC_BWD_STORE_GRADS) return MCVC_ERR_INVALID;
+    const int store = (flags & MCVC_BWD_STORE_GRADS) ? 1 : 0;
     if (!x || !dy || !dw0 || !scratch || scheme < 0 || scheme > 5 || branches < 1 || branches > 2 || (branches == 2 && !dw1)) return MCVC_ERR_INVALID;
     const LayerCtx l = layer_ctx(Cin, Cout, branches, KH, KW, stride, pad_h, pad_w);
     const int OH = conv_out(H, KH, stride, pad_h), OW = conv_out(W, KW, stride, pad_w);
@@ -2891,6 +2960,7 @@ int mcvc_layer_wgrad(const float* x, const float* dy, float* dw0, float* dw1, fl
         float* grads5[4] = {dw0, nullptr, dw1, nullptr};
         const long long xpl = mcvc_xs_plane(H, W);
         ex5.wgrad_x_xs = 1;
+        ex5.store_grads = store;
         conv_wgrad(ex5, l.c, grads5, N, H, W, CView{ex5.wv, (long long)Cin * 4 * xpl, 4 * xpl, W},
                    CView{dy, (long long)l.c.cout_tot * OH * OW, (long long)OH * OW, OW});
         return ex5.err;
@@ -2900,6 +2970,7 @@ int mcvc_layer_wgrad(const float* x, const float* dy, float* dw0, float* dw1, fl
     Exec ex = layer_exec(l.c, N, H, W, scheme, scratch, scratch_floats, stream, &err);
     if (err) return err;
     float* grads[4] = {dw0, nullptr, dw1, nullptr};
+    ex.store_grads = store;
     conv_wgrad(ex, l.c, grads, N, H, W, CView{x, (long long)Cin * H * W, (long long)H * W, W},
                CView{dy, (long long)l.c.cout_tot * OH * OW, (long long)OH * OW, OW});
     return ex.err;
@@ -2940,8 +3011,8 @@ int mcvc_trunk_layer_backward(const float* dy, const float* conv_out, const floa
     if (KW != 3 || !mcvc_wgrad_smallk_batch_applies(B, T4)) return MCVC_ERR_INVALID;
     SmallKJob jobs[2];
     int nj = 0;
-    jobs[nj++] = SmallKJob{x_in, dconv, dw, Cin, Cout, 0};
-    if (glu && dw_gate) jobs[nj++] = SmallKJob{x_in, dconv + (long long)Cout * B * T4, dw_gate, Cin, Cout, 0};
+    jobs[nj++] = SmallKJob{x_in, dconv, dw, Cin, Cout, 0, 0};
+    if (glu && dw_gate) jobs[nj++] = SmallKJob{x_in, dconv + (long long)Cout * B * T4, dw_gate, Cin, Cout, 0, 0};
     return mcvc_wgrad_smallk_batch_launch(jobs, nj, B, T4, s);
 }
 

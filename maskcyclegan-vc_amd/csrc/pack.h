@@ -59,8 +59,10 @@ struct UpdOwner {
     int e0, ne;            // emits: jobs [e0, e0 + ne) of the job table
     int flat;              // 1: plain elementwise owner, 256 elements per workgroup
     int vec4;              // 1: every tile row is a 16-byte-aligned run of a multiple of four floats
+    int covered;           // 1: the tensor's gradient writers can store (grad_store_covered, packforms.h): UpdAdam::zero == 2 leaves its gradient alone
 };
 struct UpdAdam { long long d_g, d_g2, d_m, d_v; int has_g2, zero; AdamCoef c; };     // d_*: float offsets from a parameter to its gradient(s) / moments
+// (zero: 0 leave the gradients, 1 clear them behind the read, 2 clear those of the owners that are not `covered` -- the next pass stores the rest)
 // LDS row pitch of an owner tile: the run of IB * taps floats rounded up to four, + 1 -- ODD, so that the emits that walk the output channels
 // (lane = co: the K-major forward copies, the forward Winograd sets) read 32 different banks; r4's pitch was a multiple of four (the Adam
 // phase stored float4s) and those reads were 4-way conflicts -- SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.71 (r4 PMC pass).

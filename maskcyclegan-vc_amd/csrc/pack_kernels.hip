@@ -247,12 +247,13 @@ __global__ void __launch_bounds__(256) update_net_kernel(const Twin<UpdNetKArgs>
     float* __restrict__ m = p + ad.d_m;
     float* __restrict__ v = p + ad.d_v;
     const AdamCoef c = ad.c;
+    const bool zero = ad.zero == 1 || (ad.zero == 2 && !o.covered);      // (uniform per workgroup: the owner is)
     if (o.flat) {                                     // biases, norm affine parameters: 256 elements per workgroup, at most a copy to emit
         const int i = rel * 256 + threadIdx.x;
         if (i >= o.Cout) return;
         float gr = g[i];
         if (g2) gr += g2[i];
-        if (ad.zero) { g[i] = 0.f; if (g2) g2[i] = 0.f; }
+        if (zero) { g[i] = 0.f; if (g2) g2[i] = 0.f; }
         float pn = p[i], mn = m[i], vn = v[i];
         adam_elem(pn, gr, mn, vn, c);
         p[i] = pn; m[i] = mn; v[i] = vn;
@@ -295,7 +296,7 @@ __global__ void __launch_bounds__(256) update_net_kernel(const Twin<UpdNetKArgs>
             for (int u = 0; u < U; ++u) {
                 if (!ok[u]) continue;
                 if (g2) { gg[u].x += hh[u].x; gg[u].y += hh[u].y; gg[u].z += hh[u].z; gg[u].w += hh[u].w; }
-                if (ad.zero) {
+                if (zero) {
                     *reinterpret_cast<float4*>(g + off[u]) = make_float4(0.f, 0.f, 0.f, 0.f);
                     if (g2) *reinterpret_cast<float4*>(g2 + off[u]) = make_float4(0.f, 0.f, 0.f, 0.f);
                 }
@@ -318,7 +319,7 @@ __global__ void __launch_bounds__(256) update_net_kernel(const Twin<UpdNetKArgs>
             const long long off = base + cc * row_stride + r;
             float gr = g[off];
             if (g2) gr += g2[off];
-            if (ad.zero) { g[off] = 0.f; if (g2) g2[off] = 0.f; }
+            if (zero) { g[off] = 0.f; if (g2) g2[off] = 0.f; }
             float pn = p[off], mn = m[off], vn = v[off];
             adam_elem(pn, gr, mn, vn, c);
             p[off] = pn; m[off] = mn; v[off] = vn;

@@ -143,6 +143,16 @@ static inline unsigned wino_only_forms(const ConvSpec& c) { return (c.wino || c.
 // tap-major forward copy, which serves the forward pass and, read row-major, the data gradient
 static inline unsigned igemm_only_forms(const ConvSpec& c) { return c.igemm ? form_bit(PF_BIAS) | form_bit(PF_IFWD) : kAllForms; }
 
+// Gradient store mode (MCVC_BWD_STORE_GRADS, include/mcvc.h): the layers whose weight-gradient writers can STORE a pass's gradient instead of
+// adding to what the buffer held -- the Winograd layers, the implicit-GEMM layers and the wide 1 x KW convolutions of the 1-D trunk
+// (wgrad_smallk* / wgemm).  A static predicate of the layer alone: the fused update (which gradients a zero_grads == 2 update leaves
+// uncleared) and conv_wgrad (which passes store) both read it, so the two can never disagree.  Biases, norm affine parameters and the edge
+// layers (2 input channels / 1 output channel: the atomic writers) are not covered: they are cleared and accumulated into as before.
+static inline bool grad_store_covered(const ConvSpec& c)
+{
+    return c.wino || c.wino3 || c.igemm || (c.KH == 1 && c.stride == 1 && c.Cin >= 64 && c.cout_tot >= 64);
+}
+
 static void spec_finalize(ConvSpec& c, long long& cur)
 {
     c.cout_tot = c.Cout * c.nbr;

@@ -315,7 +315,7 @@ __global__ void __launch_bounds__(256) igemm_kernel(const Twin<IGemmArgs> tw)
 }
 
 // ---- the weight gradients' K-split slabs ----------------------------------------------------------------------------------------------
-struct DwAccumKArgs { const float* slabs; int nslab; long long slab_stride; float* g0; float* g1; int Cout; int rows; int K9; };
+struct DwAccumKArgs { const float* slabs; int nslab; long long slab_stride; float* g0; float* g1; int Cout; int rows; int K9; int store; };
 __global__ void __launch_bounds__(256) dw_accum_kernel(const Twin<DwAccumKArgs> tw)
 {
     const DwAccumKArgs ka_ = tw.v[blockIdx.z];
@@ -336,6 +336,7 @@ __global__ void __launch_bounds__(256) dw_accum_kernel(const Twin<DwAccumKArgs> 
     }
     const long long split = (long long)Cout * K9;
     float4* d = reinterpret_cast<float4*>(i < split ? g0 + i : g1 + (i - split));
+    if (ka_.store) { *d = s; return; }                 // (uniform: the gradient is the slabs' sum, its old value is not read)
     float4 o = *d;
     o.x += s.x; o.y += s.y; o.z += s.z; o.w += s.w;
     *d = o;
@@ -472,11 +473,11 @@ int mcvc_igemm_launch(const IGemmArgs& a0, hipStream_t s)
     return (int)hipGetLastError();
 }
 
-int mcvc_dw_accum_launch(const float* slabs, int nslab, long long slab_stride, float* g0, float* g1, int Cout, int rows, int K9, hipStream_t s)
+int mcvc_dw_accum_launch(const float* slabs, int nslab, long long slab_stride, float* g0, float* g1, int Cout, int rows, int K9, hipStream_t s, int store)
 {
     const long long n = (long long)rows * K9;
     if ((n & 3) || (((long long)Cout * K9) & 3) || (rows > Cout && !g1)) return MCVC_ERR_INVALID;
-    TraceScope ts(K_ELEMENTWISE, s, 0.0, 4.0 * n * (nslab + 2.0));
-    mcvc_launch(dw_accum_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, DwAccumKArgs{slabs, nslab, slab_stride, g0, g1, Cout, rows, K9});
+    TraceScope ts(K_ELEMENTWISE, s, 0.0, 4.0 * n * (nslab + (store ? 1.0 : 2.0)));
+    mcvc_launch(dw_accum_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, DwAccumKArgs{slabs, nslab, slab_stride, g0, g1, Cout, rows, K9, store ? 1 : 0});
     return (int)hipGetLastError();
 }

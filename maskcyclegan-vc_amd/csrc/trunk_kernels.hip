@@ -1076,11 +1076,14 @@ __global__ void __launch_bounds__(kNetThreads) trunk_bwd_net_kernel(const Twin<T
     }
 }
 
-struct ZeroWordsKArgs { unsigned* p; int n; };
+// p[0..n) = 0: the persistent kernels' arrival counters (one workgroup), and a gradient tensor in front of a writer that can only add
+// (mcvc_zero_words_launch: conv_wgrad's store mode)
+struct ZeroWordsKArgs { unsigned* p; long long n; };
 __global__ void zero_words_kernel(const Twin<ZeroWordsKArgs> tw)
 {
     const ZeroWordsKArgs a = tw.v[blockIdx.z];
-    if ((int)threadIdx.x < a.n) a.p[threadIdx.x] = 0u;
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += step) a.p[i] = 0u;
 }
 
 // dst[c][0..per_row) = bias ? bias[c] : 0   (initial value of an atomically accumulated K-split trunk layer)
@@ -1287,5 +1290,17 @@ int mcvc_trunk_bwd_net_launch(TrunkBwdNetArgs& a, hipStream_t s)
     }
     if (wide) mcvc_launch(trunk_bwd_net_kernel<2>, dim3(kNetGrid), dim3(kNetThreads), lds, s, a);
     else mcvc_launch(trunk_bwd_net_kernel<1>, dim3(kNetGrid), dim3(kNetThreads), lds, s, a);
+    return (int)hipGetLastError();
+}
+
+// p[0..n) = 0.f on stream s, as a kernel (it takes part in grouped launches, which a memset would not)
+int mcvc_zero_words_launch(float* p, long long n, hipStream_t s)
+{
+    if (!p || n < 0) return MCVC_ERR_INVALID;
+    if (n == 0) return 0;
+    long long b = (n + 1023) / 1024;
+    if (b > 2048) b = 2048;
+    TraceScope ts(K_ELEMENTWISE, s, 0.0, 4.0 * (double)n);
+    mcvc_launch(zero_words_kernel, dim3((unsigned)b), dim3(256), 0, s, ZeroWordsKArgs{reinterpret_cast<unsigned*>(p), n});
     return (int)hipGetLastError();
 }

@@ -232,8 +232,8 @@ int mcvc_wgemm_launch(const WGemmArgs& a0, hipStream_t s)
     a.ldc = (long long)a.Cin * a.ntaps;
     const double K = (double)a.NPIX;
     const double flops = 2.0 * a.M * a.Cin * a.ntaps * K;
-    // operands once from HBM (dY; x with the taps' overlap in L2) + the gradient (read-modify-write) / the slabs
-    const double bytes = 4.0 * (K * a.M + 2.25 * K * a.Cin + (double)a.M * a.Cin * a.ntaps * (a.nsplit > 1 ? a.nsplit : 2));
+    // operands once from HBM (dY; x with the taps' overlap in L2) + the gradient (read-modify-write, or a plain store) / the slabs
+    const double bytes = 4.0 * (K * a.M + 2.25 * K * a.Cin + (double)a.M * a.Cin * a.ntaps * (a.nsplit > 1 ? a.nsplit : (a.accumulate ? 2 : 1)));
     if (a.ntaps == 9) return wgemm_launch_t<9, 32>(a, flops, bytes, s);
     if (a.ntaps == 3) return wgemm_launch_t<3, 32>(a, flops, bytes, s);
     return wgemm_launch_t<1, 64>(a, flops, bytes, s);

@@ -38,13 +38,13 @@ int mcvc_wino3_input_phase_launch(const WinoXformArgs& a, int XH, int XW, hipStr
 // dw[co][ci][2u'+p][2v'+q] += (G3^T dU G3)[u'][v'] for dU[16][Cout_tot][4*Cin]; output channels >= Cout go to dw1 (gate branch)
 int mcvc_wino3_input_phase_t_launch(const WinoXformArgs& a, int XH, int XW, hipStream_t s);
 int mcvc_wino3_dy_t_launch(const WinoXformArgs& a, hipStream_t s);
-int mcvc_wino3_dw_launch(const float* du, float* dw0, float* dw1, int Cout, int nbr, int Cin, hipStream_t s);
+int mcvc_wino3_dw_launch(const float* du, float* dw0, float* dw1, int Cout, int nbr, int Cin, int store, hipStream_t s);      // (store: dw = ..., the old values are not read)
 // weight-gradient operands, tile-major (the tile index is the contraction dimension there): Vt[36][NTp][C] from x, and
 // dMt[36][NTp][C] = A dY A^T from the 2x2 output-gradient tiles; rows of tiles >= NT are written as zeros
 int mcvc_wino_input_t_launch(const WinoXformArgs& a, hipStream_t s);
 int mcvc_wino_dy_t_launch(const WinoXformArgs& a, hipStream_t s);
 // dw[co][ci][5][5] += G^T dU G  from dU[36][Cout][Cin]
-int mcvc_wino_dw_launch(const float* du, float* dw, int Cout, int Cin, hipStream_t s);
+int mcvc_wino_dw_launch(const float* du, float* dw, int Cout, int Cin, int store, hipStream_t s);
 int mcvc_wino_output_launch(const WinoOutArgs& a, hipStream_t s);
 // Weight transform U = G g G^T, one thread per (co, ci), called from the whole-network re-pack kernel:
 // U[xi][k][col] (K-major, `ld` columns, xi_stride floats between transform points) from OIHW weights w[Cout][Cin][5][5].
@@ -219,4 +219,4 @@ int mcvc_wino43_input_phase_launch(const WinoXformArgs& a, int XH, int XW, hipSt
 int mcvc_wino43_output_launch(const WinoOutArgs& a, hipStream_t s);
 int mcvc_wino43_input_phase_t_launch(const WinoXformArgs& a, int XH, int XW, hipStream_t s);
 int mcvc_wino43_dy_t_launch(const WinoXformArgs& a, hipStream_t s);
-int mcvc_wino43_dw_launch(const float* du, float* dw0, float* dw1, int Cout, int nbr, int Cin, hipStream_t s);
+int mcvc_wino43_dw_launch(const float* du, float* dw0, float* dw1, int Cout, int nbr, int Cin, int store, hipStream_t s);

@@ -37,7 +37,7 @@ int mcvc_wino4_input_launch(const WinoXformArgs& a, hipStream_t s);      // x ->
 int mcvc_wino4_output_launch(const WinoOutArgs& a, hipStream_t s);       // M[64][Cout][NTp] -> y (+bias, PixelShuffle store, accumulate)
 int mcvc_wino4_input_t_launch(const WinoXformArgs& a, hipStream_t s);    // x -> Vt[64][NTp][C]
 int mcvc_wino4_dy_t_launch(const WinoXformArgs& a, hipStream_t s);       // dY -> dMt[64][NTp][C] = A dY A^T
-int mcvc_wino4_dw_launch(const float* du, float* dw, int Cout, int Cin, hipStream_t s);   // dw[co][ci][5][5] += G^T dU G, dU[64][Cout][Cin]
+int mcvc_wino4_dw_launch(const float* du, float* dw, int Cout, int Cin, int store, hipStream_t s);   // dw[co][ci][5][5] += G^T dU G, dU[64][Cout][Cin]
 
 // Weight transform U = G g G^T (8x8 from 5x5), one thread per (co, ci), called from the whole-network re-pack kernel; same conventions as
 // wino_weight_tile (dgrad: taps flipped, rows = output channels).

@@ -212,7 +212,9 @@ int xform43_t_launch(const WinoXformArgs& a, int XH, int XW, double bytes, hipSt
 }
 
 // dg' = G^T dU G (3x3 per (co, k = 4ci+2p+q), G = 6x3), scattered into the OIHW gradients: dw[co][ci][2u'+p][2v'+q] += dg'[u'][v']
+// STORE: dw = dg' (the four phases' taps cover a filter's 25 exactly once), the old values are not loaded
 struct W43DwKArgs { const float* du; float* dw0; float* dw1; int Cout; int nbr; int Cin; };
+template <bool STORE>
 __global__ void __launch_bounds__(256) wino43_dw_kernel(const Twin<W43DwKArgs> tw)
 {
     const W43DwKArgs ka_ = tw.v[blockIdx.z];
@@ -252,14 +254,14 @@ __global__ void __launch_bounds__(256) wino43_dw_kernel(const Twin<W43DwKArgs> t
 #pragma unroll
         for (int v = 0; v < 3; ++v) {
             const int kh = 2 * u + p, kw = 2 * v + q;
-            old[u][v] = (kh <= 4 && kw <= 4) ? dst[kh * 5 + kw] : 0.f;
+            old[u][v] = (!STORE && kh <= 4 && kw <= 4) ? dst[kh * 5 + kw] : 0.f;
         }
 #pragma unroll
     for (int u = 0; u < 3; ++u)
 #pragma unroll
         for (int v = 0; v < 3; ++v) {
             const int kh = 2 * u + p, kw = 2 * v + q;
-            if (kh <= 4 && kw <= 4) dst[kh * 5 + kw] = old[u][v] + r[u][v];
+            if (kh <= 4 && kw <= 4) dst[kh * 5 + kw] = STORE ? r[u][v] : old[u][v] + r[u][v];
         }
 }
 
@@ -299,10 +301,11 @@ int mcvc_wino43_dy_t_launch(const WinoXformArgs& a, hipStream_t s)
     return xform43_t_launch<1>(a, 0, 0, 4.0 * ((double)a.N * a.C * a.H * a.W + 36.0 * a.C * a.NTp), s);
 }
 
-int mcvc_wino43_dw_launch(const float* du, float* dw0, float* dw1, int Cout, int nbr, int Cin, hipStream_t s)
+int mcvc_wino43_dw_launch(const float* du, float* dw0, float* dw1, int Cout, int nbr, int Cin, int store, hipStream_t s)
 {
     dim3 grid((unsigned)cdiv_i(4 * Cin, 256), (unsigned)(Cout * nbr));
-    TraceScope ts(K_ELEMENTWISE, s, 0.0, 4.0 * (36.0 * 4.0 + 2.0 * 25.0) * Cout * nbr * Cin);
-    mcvc_launch(wino43_dw_kernel, grid, dim3(256), 0, s, W43DwKArgs{du, dw0, dw1, Cout, nbr, Cin});
+    TraceScope ts(K_ELEMENTWISE, s, 0.0, 4.0 * (36.0 * 4.0 + (store ? 1.0 : 2.0) * 25.0) * Cout * nbr * Cin);
+    if (store) mcvc_launch(wino43_dw_kernel<true>, grid, dim3(256), 0, s, W43DwKArgs{du, dw0, dw1, Cout, nbr, Cin});
+    else mcvc_launch(wino43_dw_kernel<false>, grid, dim3(256), 0, s, W43DwKArgs{du, dw0, dw1, Cout, nbr, Cin});
     return (int)hipGetLastError();
 }

@@ -198,8 +198,10 @@ __global__ void __launch_bounds__(256) xform4_t_kernel(const Twin<WinoXformArgs>
     }
 }
 
-// dg = G^T dU G, accumulated into the OIHW gradient.  One thread per (co, ci), ci fastest (coalesced reads of dU).
+// dg = G^T dU G, accumulated into the OIHW gradient (STORE: written over it, the old values are not loaded).  One thread per (co, ci), ci
+// fastest (coalesced reads of dU).
 struct Wino4DwKArgs { const float* du; float* dw; int Cout; int Cin; };
+template <bool STORE>
 __global__ void __launch_bounds__(256) wino4_dw_kernel(const Twin<Wino4DwKArgs> tw)
 {
     const Wino4DwKArgs a = tw.v[blockIdx.z];
@@ -234,6 +236,11 @@ __global__ void __launch_bounds__(256) wino4_dw_kernel(const Twin<Wino4DwKArgs> 
     __syncthreads();
     int nci = a.Cin - (int)blockIdx.x * 256; if (nci > 256) nci = 256;
     float* dst = a.dw + ((long long)co * a.Cin + (long long)blockIdx.x * 256) * 25;
+    if (STORE) {
+#pragma unroll
+        for (int u = 0; u < 25; ++u) { const int i = threadIdx.x + u * 256; if (i < nci * 25) dst[i] = wt[i]; }
+        return;
+    }
     float old[25];                               // (all loads of the read-modify-write before the first store)
 #pragma unroll
     for (int u = 0; u < 25; ++u) { const int i = threadIdx.x + u * 256; old[u] = (i < nci * 25) ? dst[i] : 0.f; }
@@ -277,10 +284,11 @@ static int xform4_t_launch(const WinoXformArgs& a, hipStream_t s)
 int mcvc_wino4_input_t_launch(const WinoXformArgs& a, hipStream_t s) { return xform4_t_launch<0>(a, s); }
 int mcvc_wino4_dy_t_launch(const WinoXformArgs& a, hipStream_t s) { return xform4_t_launch<1>(a, s); }
 
-int mcvc_wino4_dw_launch(const float* du, float* dw, int Cout, int Cin, hipStream_t s)
+int mcvc_wino4_dw_launch(const float* du, float* dw, int Cout, int Cin, int store, hipStream_t s)
 {
     dim3 grid((unsigned)cdiv_i(Cin, 256), (unsigned)Cout);
-    TraceScope ts(K_ELEMENTWISE, s, 0.0, 4.0 * (64.0 + 50.0) * Cout * Cin);
-    mcvc_launch(wino4_dw_kernel, grid, dim3(256), 0, s, Wino4DwKArgs{du, dw, Cout, Cin});
+    TraceScope ts(K_ELEMENTWISE, s, 0.0, 4.0 * (64.0 + (store ? 25.0 : 50.0)) * Cout * Cin);
+    if (store) mcvc_launch(wino4_dw_kernel<true>, grid, dim3(256), 0, s, Wino4DwKArgs{du, dw, Cout, Cin});
+    else mcvc_launch(wino4_dw_kernel<false>, grid, dim3(256), 0, s, Wino4DwKArgs{du, dw, Cout, Cin});
     return (int)hipGetLastError();
 }

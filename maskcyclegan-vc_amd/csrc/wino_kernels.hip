@@ -158,7 +158,9 @@ __device__ __forceinline__ void a42(float d0, float d1, float o[4]) { o[0] = d0;
 
 
 // dg' = G3^T dU G3 (3x3 per (co, k = 4ci+2p+q)), scattered into the OIHW gradient: dw[co][ci][2u'+p][2v'+q] += dg'[u'][v']
+// STORE: dw = dg' (the nine taps of the four phases cover the 25 taps of a filter exactly once), the old values are not loaded
 struct Wino3DwKArgs { const float* du; float* dw0; float* dw1; int Cout; int nbr; int Cin; };
+template <bool STORE>
 __global__ void __launch_bounds__(256) wino3_dw_kernel(const Twin<Wino3DwKArgs> tw)
 {
     const Wino3DwKArgs ka_ = tw.v[blockIdx.z];
@@ -200,14 +202,14 @@ __global__ void __launch_bounds__(256) wino3_dw_kernel(const Twin<Wino3DwKArgs> 
 #pragma unroll
         for (int v = 0; v < 3; ++v) {
             const int kh = 2 * u + p, kw = 2 * v + q;
-            old[u][v] = (kh <= 4 && kw <= 4) ? dst[kh * 5 + kw] : 0.f;
+            old[u][v] = (!STORE && kh <= 4 && kw <= 4) ? dst[kh * 5 + kw] : 0.f;
         }
 #pragma unroll
     for (int u = 0; u < 3; ++u)
 #pragma unroll
         for (int v = 0; v < 3; ++v) {
             const int kh = 2 * u + p, kw = 2 * v + q;
-            if (kh <= 4 && kw <= 4) dst[kh * 5 + kw] = old[u][v] + r[u][v];
+            if (kh <= 4 && kw <= 4) dst[kh * 5 + kw] = STORE ? r[u][v] : old[u][v] + r[u][v];
         }
 }
 
@@ -411,8 +413,10 @@ static int xform_t_launch(const WinoXformArgs& a, int XH, int XW, double bytes, 
     return (int)hipGetLastError();
 }
 
-// dg = G^T dU G, accumulated into the OIHW gradient.  One thread per (co, ci), ci fastest (coalesced reads of dU).
+// dg = G^T dU G, accumulated into the OIHW gradient (STORE: written over it, the old values are not loaded).  One thread per (co, ci), ci
+// fastest (coalesced reads of dU).
 struct WinoDwKArgs { const float* du; float* dw; int Cout; int Cin; };
+template <bool STORE>
 __global__ void __launch_bounds__(256) wino_dw_kernel(const Twin<WinoDwKArgs> tw)
 {
     const WinoDwKArgs ka_ = tw.v[blockIdx.z];
@@ -456,6 +460,11 @@ __global__ void __launch_bounds__(256) wino_dw_kernel(const Twin<WinoDwKArgs> tw
     __syncthreads();
     int nci = Cin - (int)blockIdx.x * 256; if (nci > 256) nci = 256;
     float* dst = dw + ((long long)co * Cin + (long long)blockIdx.x * 256) * 25;
+    if (STORE) {
+#pragma unroll
+        for (int u = 0; u < 25; ++u) { const int i = threadIdx.x + u * 256; if (i < nci * 25) dst[i] = wt[i]; }
+        return;
+    }
     float old[25];                               // (all loads of the read-modify-write before the first store)
 #pragma unroll
     for (int u = 0; u < 25; ++u) { const int i = threadIdx.x + u * 256; old[u] = (i < nci * 25) ? dst[i] : 0.f; }
@@ -913,11 +922,12 @@ int mcvc_wino_dy_t_launch(const WinoXformArgs& a, hipStream_t s)
     return xform_t_launch<1>(a, 0, 0, 4.0 * ((double)a.N * a.C * a.H * a.W + 36.0 * a.C * a.NTp), s);
 }
 
-int mcvc_wino_dw_launch(const float* du, float* dw, int Cout, int Cin, hipStream_t s)
+int mcvc_wino_dw_launch(const float* du, float* dw, int Cout, int Cin, int store, hipStream_t s)
 {
     dim3 grid((unsigned)cdiv_i(Cin, 256), (unsigned)Cout);
-    TraceScope ts(K_ELEMENTWISE, s, 0.0, 4.0 * (36.0 + 50.0) * Cout * Cin);
-    mcvc_launch(wino_dw_kernel, grid, dim3(256), 0, s, WinoDwKArgs{du, dw, Cout, Cin});
+    TraceScope ts(K_ELEMENTWISE, s, 0.0, 4.0 * (36.0 + (store ? 25.0 : 50.0)) * Cout * Cin);
+    if (store) mcvc_launch(wino_dw_kernel<true>, grid, dim3(256), 0, s, WinoDwKArgs{du, dw, Cout, Cin});
+    else mcvc_launch(wino_dw_kernel<false>, grid, dim3(256), 0, s, WinoDwKArgs{du, dw, Cout, Cin});
     return (int)hipGetLastError();
 }
 
@@ -955,10 +965,11 @@ int mcvc_wino3_dy_t_launch(const WinoXformArgs& a, hipStream_t s)
     return xform_t_launch<3>(a, 0, 0, 4.0 * ((double)a.N * a.C * a.H * a.W + 16.0 * a.C * a.NTp), s);
 }
 
-int mcvc_wino3_dw_launch(const float* du, float* dw0, float* dw1, int Cout, int nbr, int Cin, hipStream_t s)
+int mcvc_wino3_dw_launch(const float* du, float* dw0, float* dw1, int Cout, int nbr, int Cin, int store, hipStream_t s)
 {
     dim3 grid((unsigned)cdiv_i(4 * Cin, 256), (unsigned)(Cout * nbr));
-    TraceScope ts(K_ELEMENTWISE, s, 0.0, 4.0 * (16.0 * 4.0 + 2.0 * 25.0) * Cout * nbr * Cin);
-    mcvc_launch(wino3_dw_kernel, grid, dim3(256), 0, s, Wino3DwKArgs{du, dw0, dw1, Cout, nbr, Cin});
+    TraceScope ts(K_ELEMENTWISE, s, 0.0, 4.0 * (16.0 * 4.0 + (store ? 1.0 : 2.0) * 25.0) * Cout * nbr * Cin);
+    if (store) mcvc_launch(wino3_dw_kernel<true>, grid, dim3(256), 0, s, Wino3DwKArgs{du, dw0, dw1, Cout, nbr, Cin});
+    else mcvc_launch(wino3_dw_kernel<false>, grid, dim3(256), 0, s, Wino3DwKArgs{du, dw0, dw1, Cout, nbr, Cin});
     return (int)hipGetLastError();
 }

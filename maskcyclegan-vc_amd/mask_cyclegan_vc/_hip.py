@@ -83,6 +83,9 @@ _SIGS = {
     "mcvc_bf16_conv1_glu": (c_int, [c_void_p] * 8 + [c_int] * 2 + [c_void_p]),
     "mcvc_disc_forward": (c_int, [_PP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p]),
     "mcvc_disc_backward": (c_int, [_PP, c_void_p, _PP, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p]),
+    "mcvc_disc_backward_flags": (c_int, [_PP, c_void_p, _PP, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p,
+                                         c_int]),
+    "mcvc_grad_store_mask": (c_int, [c_int, c_int, c_void_p]),      # host only: which parameter tensors a store pass covers
     "mcvc_l1_loss": (c_int, [c_void_p, c_void_p, c_longlong, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "mcvc_lsgan_loss": (c_int, [c_void_p, c_longlong, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mcvc_loss_combine": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -148,6 +151,7 @@ _SIGS = {
     "mcvc_layer_forward": (c_int, [c_void_p] * 6 + [c_longlong] + [c_int] * 13 + [c_void_p]),
     "mcvc_layer_dgrad": (c_int, [c_void_p] * 6 + [c_longlong] + [c_int] * 12 + [c_void_p]),
     "mcvc_layer_wgrad": (c_int, [c_void_p] * 5 + [c_longlong] + [c_int] * 12 + [c_void_p]),
+    "mcvc_layer_wgrad_flags": (c_int, [c_void_p] * 5 + [c_longlong] + [c_int] * 13 + [c_void_p]),
     "mcvc_trunk_layer_backward": (c_int, [c_void_p] * 19 + [c_int] * 5 + [c_void_p]),
     "mcvc_instnorm_act_forward": (c_int, [c_void_p] * 8 + [c_int] * 5 + [c_void_p]),
     "mcvc_instnorm_act_backward": (c_int, [c_void_p] * 12 + [c_int] * 5 + [c_void_p]),

@@ -148,6 +148,14 @@ class TrainEngine:
         self._task_events = {}
         self._g_fwd_packed = False
         self._g_grad_clean = self._d_grad_clean = False
+        # Gradient store mode (include/mcvc.h MCVC_BWD_STORE_GRADS): the fused update of the grouped / pipelined schedules clears only the
+        # gradients a store pass does not cover (zero_grads = 2: biases, norm affine parameters, edge layers) and the first weight-gradient
+        # pass of the next iteration -- the cycle backward of a generator, the full / real pass of a discriminator -- STORES the covered
+        # ones (> 99 % of the parameters) instead of adding to zeros: neither the zeros' store nor their load happens.  A flat gradient
+        # buffer is then clean (all zero), dirty, or STORE-READY (uncovered tensors zero, covered ones stale: ``_x_grad_ready``); a path
+        # that would accumulate into a store-ready buffer zeroes it first (_take_grads).  False: every update clears everything (mode 1).
+        self.grad_store = True
+        self._g_grad_ready = self._d_grad_ready = False
         # Grouped launches (csrc/twin.h): G_A2B / G_B2A -- and the discriminator pairs -- run the same layer schedule on different weights,
         # so every kernel of a pair of passes goes out ONCE with gridDim.z = 2 instead of twice on two lanes: half the launches, twice the
         # workgroups per launch, the two chains in lock-step.  ``grouped_max_b``: largest per-pass batch for which the grouped schedule is
@@ -352,6 +360,38 @@ class TrainEngine:
         for ln in used:
             main.wait_stream(streams[ln])
 
+    # ---- state of the flat gradient buffers ('g' / 'd'): clean / store-ready / dirty -----------------------------------------------
+    def _take_grads(self, which, can_store=False):
+        """A phase is about to write the gradients of a group for the first time in an iteration.  Returns True when its first
+        weight-gradient pass over each network must STORE (the buffer is store-ready and the schedule can pass the flag); otherwise the
+        buffer is all zero on return (it was clean, or is zeroed here) and every pass accumulates."""
+        grp = self.g_group if which == "g" else self.d_group
+        clean, ready = getattr(self, "_%s_grad_clean" % which), getattr(self, "_%s_grad_ready" % which)
+        setattr(self, "_%s_grad_clean" % which, False)
+        setattr(self, "_%s_grad_ready" % which, False)
+        if clean:
+            return False
+        if ready and can_store and self.grad_store:
+            return True
+        grp.grad.zero_()
+        return False
+
+    def _clear_grads(self, which):
+        """Idle-lane memset of a group's gradients once their update is queued; nothing to do when the update itself left them clean or
+        store-ready."""
+        if getattr(self, "_%s_grad_clean" % which) or getattr(self, "_%s_grad_ready" % which):
+            return
+        (self.g_group if which == "g" else self.d_group).grad.zero_()
+        setattr(self, "_%s_grad_clean" % which, True)
+
+    def _grads_updated(self, which, mode):
+        """The fused update that consumed a group's gradients ran with zero_grads = ``mode`` (1: all cleared, 2: store-ready)."""
+        setattr(self, "_%s_grad_clean" % which, mode == 1)
+        setattr(self, "_%s_grad_ready" % which, mode == 2)
+
+    def _zero_mode(self):
+        return 2 if self.grad_store else 1
+
     def _aux_ptr(self, lane):
         if not self.aux_wgrad:
             return None
@@ -373,7 +413,8 @@ class TrainEngine:
         check(self.L.mcvc_gen_forward(self._p_tab[name], ptr(self.packed[name]), ptr(x), ptr(mask), ptr(out), ptr(stash), ptr(sc), sc.numel(), nb, self.T,
                                       stream()), "gen_forward")
 
-    def _G_bwd(self, name, mask, dout, dx, acc, stash, nb, lane=0, milestones=False, aux_lane=None, ms_of=None, no_join=False, stash_nb=None, stash_b0=0):
+    def _G_bwd(self, name, mask, dout, dx, acc, stash, nb, lane=0, milestones=False, aux_lane=None, ms_of=None, no_join=False, stash_nb=None, stash_b0=0,
+               store=False):
         """``lane`` picks the scratch buffer; ``aux_lane`` (default: the same) the auxiliary weight-gradient stream -- the two halves of a
         grouped pass use different scratch buffers but the same streams and milestone events (``ms_of``).  ``stash_nb``: batch of the forward
         pass that wrote ``stash`` when this pass back-propagates through its samples [stash_b0, stash_b0 + nb) only (mcvc_gen_backward_window)."""
@@ -382,19 +423,20 @@ class TrainEngine:
         aux = self._aux_ptr(lane if aux_lane is None else aux_lane)
         check(self.L.mcvc_gen_backward_window(self._p_tab[name], ptr(self.packed[name]), self._g_tab[name], ptr(mask), ptr(dout), ptr(dx), acc, ptr(stash),
                                               stash_nb or nb, stash_b0, ptr(sc), sc.numel(), nb, self.T, stream(), aux, ms,
-                                              (1 if no_join else 0) | (2 if milestones else 0)), "gen_backward")
+                                              (1 if no_join else 0) | (2 if milestones else 0) | (4 if store else 0)), "gen_backward")
 
     def _D(self, name, x, out, stash, nb, lane=0):
         sc = self.d_scratch[lane]
         check(self.L.mcvc_disc_forward(self._p_tab[name], ptr(self.packed[name]), ptr(x), ptr(out), ptr(stash), ptr(sc), sc.numel(), nb, self.T, stream()),
               "disc_forward")
 
-    def _D_bwd(self, name, dlogit, dx, acc, stash, with_weight_grads, nb, lane=0, aux_stream=None):
+    def _D_bwd(self, name, dlogit, dx, acc, stash, with_weight_grads, nb, lane=0, aux_stream=None, store=False):
         sc = self.d_scratch[lane]
         aux = ctypes.c_void_p(aux_stream.cuda_stream) if (aux_stream is not None and with_weight_grads and self.aux_wgrad) else \
             (self._aux_ptr(lane) if (with_weight_grads and self.aux_wgrad_d) else None)
-        check(self.L.mcvc_disc_backward(self._p_tab[name], ptr(self.packed[name]), self._g_tab[name] if with_weight_grads else None, ptr(dlogit), 1,
-                                        ptr(dx), acc, ptr(stash), ptr(sc), sc.numel(), nb, self.T, stream(), aux), "disc_backward")
+        check(self.L.mcvc_disc_backward_flags(self._p_tab[name], ptr(self.packed[name]), self._g_tab[name] if with_weight_grads else None, ptr(dlogit), 1,
+                                              ptr(dx), acc, ptr(stash), ptr(sc), sc.numel(), nb, self.T, stream(), aux,
+                                              4 if (store and with_weight_grads) else 0), "disc_backward")
 
     def _slot(self, i):
         return self.slots[i:i + 1]
@@ -418,13 +460,14 @@ class TrainEngine:
 
     def _update_gen(self, name, range_mask, lr, step, zero=True):
         """optimizer.step() on the parameter ranges ``range_mask`` of ONE generator fused with the refresh of every packed copy derived
-        from them (train.py:242; mcvc_gen_update_ranges).  ``zero``: clear the gradient behind the read.  The raw-pointer update does not
+        from them (train.py:242; mcvc_gen_update_ranges).  ``zero``: clear the gradient behind the read (2: only the tensors a store pass does
+        not cover, see ``grad_store``).  The raw-pointer update does not
         bump the parameters' autograd version counters: the module's own packed-weight caches are dropped so that a later module-API
         forward (validation, in-process inference) re-packs from the new values."""
         grp = self.g_group
         check(self.L.mcvc_gen_update_ranges(self._p_tab[name], self._numel[name], ptr(self.packed[name]), self._per_pass() * self._max_B, self.T,
                                             range_mask, ptr(grp.flat), ptr(grp.grad), None, ptr(grp.exp_avg), ptr(grp.exp_avg_sq), float(lr),
-                                            self.betas[0], self.betas[1], self.eps, step, self.reducer.grad_scale, 1 if zero else 0, stream()),
+                                            self.betas[0], self.betas[1], self.eps, step, self.reducer.grad_scale, int(zero), stream()),
               "gen_update " + name)
         self.nets[name]._packed_version = None
         self.nets[name]._bf16_version = None
@@ -434,7 +477,7 @@ class TrainEngine:
         grp = self.d_group
         check(self.L.mcvc_disc_update_batch(self._p_tab[name], self._numel[name], ptr(self.packed[name]), 2 * self._max_B, self.T,
                                             ptr(grp.flat), ptr(grp.grad), None, ptr(grp.exp_avg), ptr(grp.exp_avg_sq), float(lr),
-                                            self.betas[0], self.betas[1], self.eps, step, self.reducer.grad_scale, 1 if zero else 0, stream()),
+                                            self.betas[0], self.betas[1], self.eps, step, self.reducer.grad_scale, int(zero), stream()),
               "disc_update " + name)
         self.nets[name]._packed_version = None
 
@@ -460,10 +503,7 @@ class TrainEngine:
         m = self.mel
         sc = self.sched
         self.slots[:_BLOCK].zero_()
-        if self._g_grad_clean:
-            self._g_grad_clean = False           # (zeroed on an idle lane during the previous discriminator phase)
-        else:
-            self.g_group.grad.zero_()
+        self._take_grads("g")                    # (usually clean: zeroed on an idle lane during the previous discriminator phase)
         # batched inputs (device-to-device copies; the batch dimension is outermost, so halves are contiguous views)
         torch._foreach_copy_([self.in_A2B[:B], self.in_A2B[B:], self.in_B2A[:B], self.in_B2A[B:], self.mask_A2B[:B], self.mask_B2A[:B]],
                              [real_A, real_B, real_B, real_A, mask_A, mask_B])     # one launch; the masks' second halves stay all-ones
@@ -504,11 +544,10 @@ class TrainEngine:
 
         def finish_d(ln):                      # data parallel: the D gradient all-reduce of the previous iteration runs behind the
             self._finish_d_update()            # generator forwards; lane 2 is the first to need the discriminators
-            if fuse_update and not self._d_grad_clean:
+            if fuse_update:
                 # the discriminator gradients are free once their Adam step is queued: clear them here, on an idle lane, instead of
                 # on the caller's stream at the top of the discriminator phase (99 MB memset)
-                self.d_group.grad.zero_()
-                self._d_grad_clean = True
+                self._clear_grads("d")
         ov = self.overlap_g_reduce
         if fuse_update:
             self.g_group.step += 1
@@ -558,10 +597,11 @@ class TrainEngine:
         return self.grouped and self.B <= self.grouped_max_b
 
     # ---- grouped schedule: the two phases as parts that the plain and the pipelined step assemble into task graphs ----------------
-    def _g_parts(self, inp, fuse_update, own_d_update=True, zeroing_update=False, ranged=False):
+    def _g_parts(self, inp, fuse_update, own_d_update=True, zeroing_update=False, ranged=False, can_store=True):
         """Closures of the generator phase (train.py:195-242) in grouped launches.  ``own_d_update``: the first-step adversarial pair
         completes a deferred discriminator update itself (plain step); the pipelined step orders the discriminators' update in front of
-        the adversarial pairs through the task graph instead."""
+        the adversarial pairs through the task graph instead.  ``zeroing_update``: zero_grads mode of the update (0 / 1 / 2); ``can_store``:
+        the cycle backward -- the first weight-gradient pass over both generators -- may store into a store-ready buffer (``take``)."""
         real_A, mask_A, real_B, mask_B = inp
         B, B2 = self.B, 2 * self.B
         m = self.mel
@@ -578,17 +618,19 @@ class TrainEngine:
         ident_dead = il == 0                   # (after the identity cut-off the identity passes are dead code: see generator_phase)
         nbt = B if ident_dead else B2          # (the halves of the batched buffers are contiguous: translation first, identity second)
         g_lr = sc.g_opt_lr
+        zero_mode = int(zeroing_update)
         P = {}
+        st = {"store": False}                  # the cycle backward stores (set by take(), before the tasks run)
 
         copies = ([self.in_A2B[:B], self.in_A2B[B:], self.in_B2A[:B], self.in_B2A[B:], self.mask_A2B[:B], self.mask_B2A[:B]],
                   [real_A, real_B, real_B, real_A, mask_A, mask_B])                    # (the masks' second halves stay all-ones)
+        def take():
+            st["store"] = self._take_grads("g", can_store)
+
         def pre(zero_grads=True):              # on the caller's stream, before the lanes fork
             self.slots[:_BLOCK].zero_()
             if zero_grads:
-                if self._g_grad_clean:
-                    self._g_grad_clean = False
-                else:
-                    self.g_group.grad.zero_()
+                take()
             torch._foreach_copy_(*copies)      # one launch
 
         def fwd2(ln):                                                                                       # :203, :205, :207-210
@@ -619,17 +661,16 @@ class TrainEngine:
             if own_d_update:
                 self._finish_d_update()        # data parallel: the D all-reduce of the previous iteration hides behind the generator forwards
             self._twin(lambda: adv_half("discriminator_A", 0, fake_A, g_fake_A, 0), lambda: adv_half("discriminator_B", 1, fake_B, g_fake_B, 0))
-            if own_d_update and fuse_update and not self._d_grad_clean:
-                self.d_group.grad.zero_()      # free once their Adam step is queued: cleared here, on the side lane (99 MB memset)
-                self._d_grad_clean = True
+            if own_d_update and fuse_update:
+                self._clear_grads("d")         # free once their Adam step is queued: cleared here, on the side lane (99 MB memset)
 
         def adv2(ln):
             self._twin(lambda: adv_half("discriminator_A2", 2, m["cycle_A"], m["g_cycle_A"], 1),
                        lambda: adv_half("discriminator_B2", 3, m["cycle_B"], m["g_cycle_B"], 1))
 
         def bwd_cycle(ln):      # cycle_A = G_B2A(fake_B) adds to d(fake_B), cycle_B = G_A2B(fake_A) to d(fake_A)
-            self._twin(lambda: self._G_bwd(B2A, None, m["g_cycle_A"], g_fake_B, 1, self.g_stash1[0], B, 0, aux_lane=0),
-                       lambda: self._G_bwd(A2B, None, m["g_cycle_B"], g_fake_A, 1, self.g_stash1[1], B, 1, aux_lane=0))
+            self._twin(lambda: self._G_bwd(B2A, None, m["g_cycle_A"], g_fake_B, 1, self.g_stash1[0], B, 0, aux_lane=0, store=st["store"]),
+                       lambda: self._G_bwd(A2B, None, m["g_cycle_B"], g_fake_A, 1, self.g_stash1[1], B, 1, aux_lane=0, store=st["store"]))
 
         def bwd_final(ln):      # the last pass over each generator; its gradient ranges become final one after the other (milestone events)
             self._twin(lambda: self._G_bwd(A2B, self.mask_A2B, self.gout_A2B, None, 0, self.g_stash2[0], nbt, 0, ms_on, aux_lane=0, ms_of=A2B),
@@ -647,7 +688,7 @@ class TrainEngine:
 
         def update(ln):         # optimizer step of both generators + every packed copy, one grouped launch (train.py:242)
             self.reducer.wait(self.device)             # (no-op on one GPU)
-            self._update_gens(g_lr, zero=zeroing_update)
+            self._update_gens(g_lr, zero=zero_mode)
 
         def update_range(k, last):
             """Optimizer step (+ re-pack) of part k of both generators as grouped launches: 0 = up-sampling blocks + last conv, 1 = residual
@@ -662,13 +703,13 @@ class TrainEngine:
                 if k == 0:
                     self.g_group.step += 1
                 step = self.g_group.step
-                self._twin(lambda: self._update_gen(A2B, mask, g_lr, step), lambda: self._update_gen(B2A, mask, g_lr, step))
+                self._twin(lambda: self._update_gen(A2B, mask, g_lr, step, zero_mode), lambda: self._update_gen(B2A, mask, g_lr, step, zero_mode))
             return run
 
         def post():
             self._g_fwd_packed = bool(fuse_update)
             self._combine(0, self._comb_g)
-        P.update(update_range=update_range, pre=pre, fwd2=fwd2, cycle=cycle, adv1=adv1, adv2=adv2, bwd_cycle=bwd_cycle, bwd_final=bwd_final,
+        P.update(update_range=update_range, pre=pre, take=take, zero_mode=zero_mode, fwd2=fwd2, cycle=cycle, adv1=adv1, adv2=adv2, bwd_cycle=bwd_cycle, bwd_final=bwd_final,
                  queue_reduce=queue_reduce, update=update, post=post, ov=ov, copies=copies)
         return P
 
@@ -677,7 +718,7 @@ class TrainEngine:
         ``generator_phase`` on two lanes.  Lane 0: both translation (+ identity) passes, both cycle passes, the second-step discriminators,
         both backward rounds, the update.  Lane 1: the first-step adversarial pair D_A(fake_A) | D_B(fake_B), which needs only the
         translated batches and runs beside the cycle forwards."""
-        p = self._g_parts((real_A, mask_A, real_B, mask_B), fuse_update, zeroing_update=bool(fuse_update))
+        p = self._g_parts((real_A, mask_A, real_B, mask_B), fuse_update, zeroing_update=self._zero_mode() if fuse_update else 0)
         p["pre"]()
         ov = p["ov"]
         self._run_tasks([
@@ -690,13 +731,14 @@ class TrainEngine:
         ] + ([(1, p["queue_reduce"], (), None)] if (fuse_update and ov) else [])
           + ([(0, p["update"], (), None)] if fuse_update else []))
         if fuse_update:
-            self._g_grad_clean = True          # (cleared by the update launch that consumed them)
+            self._grads_updated("g", p["zero_mode"])          # (cleared, or left store-ready, by the update launch that consumed them)
         p["post"]()
 
-    def _d_parts(self, inp, gi=0, aux2=None):
+    def _d_parts(self, inp, gi=0, aux2=None, can_store=True):
         """Closures of the discriminator phase (train.py:247-299) in grouped launches.  ``gi``: index of the (stash, scratch) pair its two
         generator forwards use -- 0 = the cycle passes' (plain step: the phases run one after the other), 2 = their own (pipelined step:
-        they run beside the next iteration's generator phase)."""
+        they run beside the next iteration's generator phase).  ``can_store``: each discriminator's first weight-gradient pass (full, or
+        the real half of a split phase) may store into a store-ready buffer (``take``)."""
         real_A, mask_A, real_B, mask_B = inp
         B, B2 = self.B, 2 * self.B
         di = self.d_in
@@ -708,15 +750,16 @@ class TrainEngine:
         gst = self.g_stash1 if gi == 0 else self.g_stashD
         s0, s1 = (0, 1) if gi == 0 else (4, 5)
         P = {}
+        st = {"store": False}
 
         copies = ([di["discriminator_A"][:B], di["discriminator_A2"][:B], di["discriminator_B"][:B], di["discriminator_B2"][:B]], [real_A, real_A, real_B, real_B])
+        def take():
+            st["store"] = self._take_grads("d", can_store)
+
         def pre(zero_grads=True):
             self.slots[_BLOCK:].zero_()
             if zero_grads:
-                if self._d_grad_clean:
-                    self._d_grad_clean = False
-                else:
-                    self.d_group.grad.zero_()
+                take()
             torch._foreach_copy_(*copies)
 
         def disc_full(name):
@@ -725,15 +768,15 @@ class TrainEngine:
             self._lsgan(do[i][:B], 1.0, 0.25, 8 + 2 * i, dl[i][:B])            # every term of d_loss weighs 1/4 (:276-294)
             self._lsgan(do[i][B:], 0.0, 0.25, 9 + 2 * i, dl[i][B:])
             # (pipelined step: the second-step pair closes the critical chain; its weight gradients run on an idle lane's stream)
-            self._D_bwd(name, dl[i], None, 0, ds[i], True, B2, i, aux_stream=aux2 if i >= 2 else None)
+            self._D_bwd(name, dl[i], None, 0, ds[i], True, B2, i, aux_stream=aux2 if i >= 2 else None, store=st["store"])
 
         def disc_half(name, fake):
             i = idx[name]
             sl = slice(B, B2) if fake else slice(0, B)
-            st = ds[i] if fake else self.d_stash1[i]
-            self._D(name, di[name][sl], do[i][sl], st, B, i)
+            stash = ds[i] if fake else self.d_stash1[i]
+            self._D(name, di[name][sl], do[i][sl], stash, B, i)
             self._lsgan(do[i][sl], 0.0 if fake else 1.0, 0.25, 8 + 2 * i + int(fake), dl[i][sl])
-            self._D_bwd(name, dl[i][sl], None, 0, st, True, B, i)
+            self._D_bwd(name, dl[i][sl], None, 0, stash, True, B, i, store=st["store"] and not fake)      # (the real half runs first)
 
         def pair(fn, a, b, *args):
             return lambda ln: self._twin(lambda: fn(a, *args), lambda: fn(b, *args))
@@ -751,7 +794,7 @@ class TrainEngine:
 
         def post():
             self._combine(8, self._comb_d)
-        P.update(pre=pre, gen_fwd=gen_fwd, cycles=cycles, repack_full=repack_full, post=post, copies=copies,
+        P.update(pre=pre, take=take, gen_fwd=gen_fwd, cycles=cycles, repack_full=repack_full, post=post, copies=copies,
                  full1=pair(disc_full, "discriminator_A", "discriminator_B"), full2=pair(disc_full, "discriminator_A2", "discriminator_B2"),
                  real1=pair(disc_half, "discriminator_A", "discriminator_B", False), real2=pair(disc_half, "discriminator_A2", "discriminator_B2", False),
                  fake1=pair(disc_half, "discriminator_A", "discriminator_B", True), fake2=pair(disc_half, "discriminator_A2", "discriminator_B2", True))
@@ -771,9 +814,8 @@ class TrainEngine:
             p["gen_fwd"](ln)
 
         def refresh(ln):                       # beside the generator forwards; the generator gradients are free by now
-            if packed and not self._g_grad_clean:
-                self.g_group.grad.zero_()      # (196 MB memset on the side lane instead of at the top of the next iteration)
-                self._g_grad_clean = True
+            if packed:
+                self._clear_grads("g")         # (196 MB memset on the side lane instead of at the top of the next iteration)
         if self.B >= self.split_d_min_batch:
             # the real halves need nothing from the generators: lane 1 runs them while lane 0 is in the generator forwards
             tasks = [
@@ -796,7 +838,7 @@ class TrainEngine:
         self._run_tasks(tasks)
         p["post"]()
 
-    def _d_pair_update(self, pair, d_lr, d_step):
+    def _d_pair_update(self, pair, d_lr, d_step, zero_mode=1):
         """Task: optimizer step of one discriminator pair (its slice of the flat buffer; data parallel: behind its all-reduce) fused with the
         refresh of its packed copies -- one grouped launch (train.py:299)."""
         lo, hi = self._d_ranges[pair[0]][0], self._d_ranges[pair[1]][1]
@@ -805,7 +847,7 @@ class TrainEngine:
             if self.reducer.active:
                 self.reducer.reduce_range_after_(self.d_group.grad, lo, hi, None)
                 self.reducer.wait(self.device)
-            self._twin(lambda: self._update_disc(pair[0], d_lr, d_step), lambda: self._update_disc(pair[1], d_lr, d_step))
+            self._twin(lambda: self._update_disc(pair[0], d_lr, d_step, zero_mode), lambda: self._update_disc(pair[1], d_lr, d_step, zero_mode))
         return run
 
     # ---- pipelined step ------------------------------------------------------------------------------------------------------------
@@ -829,7 +871,8 @@ class TrainEngine:
         cur = self.static_in
         prev, d_lr = self._pending_D if self._pending_D is not None else (None, None)
         ranged = not self.reducer.active
-        g = self._g_parts(cur, True, own_d_update=prev is None, zeroing_update=True, ranged=ranged)
+        zm = self._zero_mode()
+        g = self._g_parts(cur, True, own_d_update=prev is None, zeroing_update=zm, ranged=ranged)
         ov = g["ov"]
         if prev is None:                       # first iteration (or the first after a flush): there is no discriminator phase to run beside it
             g["pre"](zero_grads=True)
@@ -837,10 +880,11 @@ class TrainEngine:
                      (0, g["bwd_cycle"], ("d1",), None), (0, g["bwd_final"], (), "f")]
             tasks += ([(3, g["queue_reduce"], (), None)] if ov else []) + [(0, g["update"], (), None)]
             self._run_tasks(tasks)
-            self._g_grad_clean = True          # (cleared by the update launch that consumed them)
+            self._grads_updated("g", zm)       # (cleared, or left store-ready, by the update launch that consumed them)
             g["post"]()
             return
         d = self._d_parts(prev, gi=2, aux2=self._sides[1])            # (lane 2's stream: idle until "dupd1")
+        g["take"](), d["take"]()               # (no memset: the updates that consumed the gradients cleared them or left them store-ready)
         # caller's stream, before the lanes fork, TWO launches (five until r5, ~15 us of idle GPU each at the head of the chain): iteration t's g_loss
         # terms saved + both phases' input copies; both loss blocks cleared (the gradients were cleared by the updates that consumed them)
         torch._foreach_copy_([self.slots_done[:_BLOCK]] + g["copies"][0] + d["copies"][0], [self.slots[:_BLOCK]] + g["copies"][1] + d["copies"][1])
@@ -859,9 +903,9 @@ class TrainEngine:
         tasks += ([] if serial else [(1, d["cycles"], (), "cyc")]) + [
             (0, g["cycle"], (), None),
             (3, d["fake1"] if split else d["full1"], ("gen",), None),
-            (3, self._d_pair_update(("discriminator_A", "discriminator_B"), d_lr, d_step), (), "dupd1"),
+            (3, self._d_pair_update(("discriminator_A", "discriminator_B"), d_lr, d_step, zm), (), "dupd1"),
             (1, d["fake2"] if split else d["full2"], ("r2",) if split else (), None),
-            (1, self._d_pair_update(("discriminator_A2", "discriminator_B2"), d_lr, d_step), (), "dupd2"),
+            (1, self._d_pair_update(("discriminator_A2", "discriminator_B2"), d_lr, d_step, zm), (), "dupd2"),
             (2, g["adv1"], ("g", "dupd1"), "d1"),
         ] + ([(2, lambda ln: (d["post"](), self.slots_done[_BLOCK:].copy_(self.slots[_BLOCK:]), self._publish_done()), ("dupd2",), None)] if tail else []) + [
             (0, g["adv2"], ("dupd2",), None),
@@ -880,7 +924,7 @@ class TrainEngine:
             tasks += [(0, g["update"], ("cyc",), None)]
         self._run_tasks(tasks)
         self.d_group.step = d_step
-        self._g_grad_clean = self._d_grad_clean = True
+        self._grads_updated("g", zm), self._grads_updated("d", zm)
         if not tail:      # (tail: the loss sums and the publish of iteration t's losses ride on lanes 1 / 2 instead of the end of the chain)
             g["post"](), d["post"](), self.slots_done[_BLOCK:].copy_(self.slots[_BLOCK:]), self._publish_done()
 
@@ -920,7 +964,7 @@ class TrainEngine:
         sc = self.sched
         cl, il = sc.cycle_loss_lambda, sc.identity_loss_lambda
         ranged = not self.reducer.active
-        g = self._g_parts(cur, True, own_d_update=False, zeroing_update=True, ranged=ranged)     # (update / reduce / post closures)
+        g = self._g_parts(cur, True, own_d_update=False, zeroing_update=1, ranged=ranged, can_store=False)     # (update / reduce / post closures; no store mode)
         ov = g["ov"]
         ms_on = ov or ranged
         real_A, mask_A, real_B, mask_B = cur
@@ -935,13 +979,12 @@ class TrainEngine:
         m = self.mel
         di = self.d_in
         do, dl, ds = self.dout1, self.dlogit1, self.d_stash1
-        d = self._d_parts(prev, gi=2, aux2=None) if prev is not None else None
+        d = self._d_parts(prev, gi=2, aux2=None, can_store=False) if prev is not None else None
         if prev is not None:
             self.slots_done[:_BLOCK].copy_(self.slots[:_BLOCK])       # g_loss and its terms of iteration t, before the block is reused
         # ---- on the caller's stream, before the lanes fork
         self.slots[:_BLOCK].zero_()
-        if not self._g_grad_clean:
-            self.g_group.grad.zero_()
+        self._take_grads("g")
         torch._foreach_copy_(
             [in3[A2B][:B], in3[A2B][B:B2], in3[A2B][B2:], mask3[A2B][B:B2], mask3[A2B][B2:],
              in3[B2A][:B], in3[B2A][B:B2], in3[B2A][B2:], mask3[B2A][B:B2], mask3[B2A][B2:]],
@@ -1005,11 +1048,11 @@ class TrainEngine:
         else:
             tasks += [(0, g["update"], (), None)]
         self._run_tasks(tasks)
-        self._g_grad_clean = True              # (cleared by the update launches that consumed them)
+        self._grads_updated("g", 1)            # (cleared by the update launches that consumed them)
         g["post"]()
         if d is not None:
             self.d_group.step = d_step
-            self._d_grad_clean = True
+            self._grads_updated("d", 1)
             d["post"]()
             self.slots_done[_BLOCK:].copy_(self.slots[_BLOCK:])           # d_loss and its terms of iteration t: the iteration is complete
             self._publish_done()
@@ -1041,10 +1084,7 @@ class TrainEngine:
         """train.py:247-299 on four lanes."""
         B, B2 = self.B, 2 * self.B
         self.slots[_BLOCK:].zero_()
-        if self._d_grad_clean:
-            self._d_grad_clean = False
-        else:
-            self.d_group.grad.zero_()
+        self._take_grads("d")
         di = self.d_in
         # generators run with their UPDATED weights and no gradient (train.py:259-273); outputs land directly in the
         # second half of the discriminators' batched inputs
@@ -1074,7 +1114,7 @@ class TrainEngine:
 
             def clear_g(ln):
                 self.g_group.grad.zero_()      # the generator gradients are free (their update ended the generator phase): 196 MB
-                self._g_grad_clean = True      # memset on an idle lane instead of at the top of the next iteration
+                self._grads_updated("g", 1)    # memset on an idle lane instead of at the top of the next iteration
             head = [
                 (0, lambda ln: self._G("generator_A2B", real_A, mask_A, gen_B, self.g_stash1[0], B, ln), (), "gB"),      # :267 generated_B
                 (1, lambda ln: self._G("generator_B2A", real_B, mask_B, gen_A, self.g_stash1[1], B, ln), (), "gA"),      # :259 generated_A
@@ -1169,8 +1209,8 @@ class TrainEngine:
             self.slots_done[:_BLOCK].copy_(self.slots[:_BLOCK])
             self.discriminator_phase_grouped(*inp)
             self.reducer.reduce_(self.d_group.grad)
-            self._update_discs(d_lr, zero=True)
-            self._d_grad_clean = True
+            self._update_discs(d_lr, zero=self._zero_mode())
+            self._grads_updated("d", self._zero_mode())
             self.slots_done[_BLOCK:].copy_(self.slots[_BLOCK:])
             self._publish_done()
         self._finish_d_update()
