@@ -221,6 +221,22 @@ int mcvc_gen_infer_bf16(const float* const* params, const void* packed, const fl
 long long mcvc_bf16_conv2d_pack_bytes(int Cout, int Cin, int KH, int KW);
 int mcvc_bf16_conv2d(const void* x, const float* w, const float* bias, void* y, void* wpack, int N, int H, int W, int Cin, int Cout,
                      int KH, int KW, int stride, int pad_h, int pad_w, void* stream);
+/*      Host view of what the bf16 convolution launcher decides for a problem (pure host code, no device call; the launcher runs this very
+ *      plan).  mcvc_bf16_conv_plan: the problem of mcvc_bf16_conv2d with the same arguments (same Cout padding); returns what that launch
+ *      would return, 0 or MCVC_ERR_INVALID, and fills out[0..12] (n_out >= 13) with
+ *        cfg (tile configuration: 0 = 128 x 128, 1 = 64 x 64, 2 = 32 x 128, 3 = 128 x 64, 4 = 128 x 256, 5 = 128 x 512), BM, BN,
+ *        KWT, PPT (the instantiated compile-time kernel width and input-prefetch depth; 0 = run-time width / synchronous staging),
+ *        TH, TW (pixel tile), tiles_h, tiles_w, PH, PW (staged input patch: rows, row pitch in pixels), LDS bytes,
+ *        1 when the kernel maps workgroups to tiles XCD-wise (0: channel tile = block % channel tiles).
+ *      Fields decided before a rejection are filled, the rest are 0 (cfg = -1 when nothing was decided).
+ *      mcvc_gen_bf16_conv_plans: one row of 14 ints {layer id, the 13 fields} per convolution that mcvc_gen_infer_bf16(B, T) runs on the
+ *      generic kernel, in call order -- the forward itself in a plan-only mode, so fused layers (no row) and the unfused trunk are chosen as
+ *      a real call chooses them.  Layer ids: 0 conv1, 1 downSample1, 2 downSample2, 3 conv2dto1d, 4 conv1dto2d, 5 upSample1, 6 upSample2,
+ *      7 last conv, 10 + i / 20 + i the value|gate / output convolution of residual block i.  *n = rows of the plan; returns the first
+ *      layer's error if a layer has no valid plan (what the forward would return), MCVC_ERR_WORKSPACE when cap is smaller than *n (the first
+ *      cap rows are written), else 0.                                                                                                  */
+int mcvc_bf16_conv_plan(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_h, int pad_w, int* out, int n_out);
+int mcvc_gen_bf16_conv_plans(int B, int T, int* rows, int cap, int* n);
 /*      conv1 of the bf16 forward with its input preparation and gated GLU fused (r6; model.py:241-242):
  *      y[B][80][T][128] bf16 NHWC = conv2d(stack(x * mask, mask), w, b, padding (2, 7)) * sigmoid(conv2d(..., wg, bg)); x, mask fp32 [B][80][T]
  *      (mask NULL = ones), w / wg [128][2][5][15], b / bg [128] fp32; wpack: mcvc_bf16_conv1_glu_pack_bytes() bytes, 16-byte aligned.     */

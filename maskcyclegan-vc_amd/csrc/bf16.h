@@ -24,6 +24,16 @@ struct Bf16ConvArgs {
     int glu;                            // 1: rows [0, Cout_pad/2) are value channels, [Cout_pad/2, Cout_pad) their gates, interleaved per
                                         //    64-row block by the packer; the epilogue stores value * sigmoid(gate): Cout = Cout_pad / 2
 };
+// What the launcher decides for a problem, as plain host data (no HIP call): tile configuration, the kernel instantiation
+// bf16_conv_kernel<.., KWT, PPT> (0 = run-time kernel width / synchronous patch staging), pixel tile, staged patch, LDS bytes and whether
+// the kernel maps workgroups to tiles XCD-wise.  mcvc_bf16_conv_launch launches exactly this plan.
+struct Bf16ConvPlan {
+    int cfg, BM, BN, KWT, PPT;
+    int TH, TW, tiles_h, tiles_w, PH, PW;
+    int lds_bytes, xcd_map;
+};
+// fills the launcher-chosen fields of `a` (TH .. wbufs) and `p`; returns what the launch would return for `a`: 0 or MCVC_ERR_INVALID
+int mcvc_bf16_conv_make_plan(Bf16ConvArgs& a, Bf16ConvPlan& p);
 int mcvc_bf16_conv_launch(const Bf16ConvArgs& a, hipStream_t s);
 // pixel-tile shape for an OH x OW output grid (TH * TW = bn)
 void mcvc_bf16_conv_tile(int OH, int OW, int KH, int KW, int stride, int bn, int* TH, int* tw_log2);

@@ -57,6 +57,9 @@ constexpr int kConvThreads = 256;
 constexpr int kMaxWP = 10;          // 16-byte weight pieces per thread and stage (BM * KW * 4 <= 2560)
 // 16-byte input-patch pieces per thread that are prefetched through registers one channel chunk ahead: template parameter PPT
 // (4 for stride-1 layers, 12 for the stride-2 layers whose patch is ~4x larger)
+// the test by which bf16_conv_kernel maps workgroups to tiles XCD-wise, restated for the plan that reports it (the kernel keeps its own
+// copy: routed through a shared function it compiled to different code)
+inline bool conv_xcd_map(int n_co, int n_px) { return n_co <= 8 && (8 % n_co) == 0 && (n_px % (8 / n_co)) == 0; }
 
 // KWT > 0: the kernel width is a compile-time constant (taps fully unrolled: the compiler hoists the next operands' LDS reads above
 // the current MFMAs); KWT == 0: run-time width.
@@ -84,7 +87,7 @@ __global__ void __launch_bounds__(kConvThreads) bf16_conv_kernel(const Bf16ConvA
     int co_tile, px_tile;
     {
         const int b = blockIdx.x;
-        if (n_co <= 8 && (8 % n_co) == 0 && (n_px % (8 / n_co)) == 0) {
+        if (n_co <= 8 && (8 % n_co) == 0 && (n_px % (8 / n_co)) == 0) {        // (conv_xcd_map: the plan reports this test)
             const int xcd = b & 7, j = b >> 3, per = 8 / n_co;
             co_tile = xcd % n_co;
             px_tile = j * per + xcd / n_co;
@@ -472,12 +475,34 @@ int bf16_prefetch_depth(int pieces, int KW, int BM, int BN)
     return 0;
 }
 
+// The instantiation <KWT, PPT> of a BM x BN tile for kernel width KW and prefetch depth `depth`: the plan's statement of what
+// conv_launch_kw below compiles -- a pair it has no instantiation for is an error there, so the two cannot drift apart silently.
+void bf16_conv_form(int KW, int depth, int BM, int BN, int* KWT, int* PPT)
+{
+    *KWT = 0; *PPT = 0;
+    if (KW == 5) {
+        *KWT = 5;
+        if (depth == 4 || depth == 12) *PPT = depth;
+        else if (BM == 128 && BN == 512 && (depth == 13 || depth == 17)) *PPT = depth;
+        else if (BM == 128 && BN == 256 && depth == 20) *PPT = depth;
+    } else if (KW == 3) {
+        *KWT = 3;
+        if (depth == 4 || depth == 12) *PPT = depth;
+    } else if (KW == 6 && BM == 64 && BN == 64 && (depth == 4 || depth == 12)) {
+        *KWT = 6; *PPT = depth;            // (the 1-D trunk of the inference forward: three taps x two channel groups, stride 2)
+    } else if (KW == 1 && depth == 4) {
+        *KWT = 1; *PPT = 4;
+    }
+}
+
 template <int WM, int WN, int MT, int NT>
-int conv_launch_kw(const Bf16ConvArgs& a, size_t lds, hipStream_t s)
+int conv_launch_kw(const Bf16ConvArgs& a, const Bf16ConvPlan& p, hipStream_t s)
 {
     constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
-    const int depth = bf16_prefetch_depth(a.PH * a.PW * 4, a.KW, BM, BN);
-    if (a.KW == 5) {
+    const size_t lds = (size_t)p.lds_bytes;
+    const int kwt = p.KWT, depth = p.PPT;
+    if (p.BM != BM || p.BN != BN || (kwt != 0 && kwt != a.KW)) return MCVC_ERR_INVALID;
+    if (kwt == 5) {
         if (depth == 4) return conv_launch_t<WM, WN, MT, NT, 5, 4>(a, lds, s);
         if (depth == 12) return conv_launch_t<WM, WN, MT, NT, 5, 12>(a, lds, s);
         if constexpr (BM == 128 && BN == 512) {
@@ -487,19 +512,20 @@ int conv_launch_kw(const Bf16ConvArgs& a, size_t lds, hipStream_t s)
         if constexpr (BM == 128 && BN == 256) {
             if (depth == 20) return conv_launch_t<WM, WN, MT, NT, 5, 20>(a, lds, s);
         }
-        return conv_launch_t<WM, WN, MT, NT, 5, 0>(a, lds, s);
+        if (depth == 0) return conv_launch_t<WM, WN, MT, NT, 5, 0>(a, lds, s);
     }
-    if (a.KW == 3) {
+    if (kwt == 3) {
         if (depth == 4) return conv_launch_t<WM, WN, MT, NT, 3, 4>(a, lds, s);
         if (depth == 12) return conv_launch_t<WM, WN, MT, NT, 3, 12>(a, lds, s);
-        return conv_launch_t<WM, WN, MT, NT, 3, 0>(a, lds, s);
+        if (depth == 0) return conv_launch_t<WM, WN, MT, NT, 3, 0>(a, lds, s);
     }
-    if constexpr (BM == 64 && BN == 64) {          // (the 1-D trunk of the inference forward: three taps x two channel groups, stride 2)
-        if (a.KW == 6 && depth == 4) return conv_launch_t<WM, WN, MT, NT, 6, 4>(a, lds, s);
-        if (a.KW == 6 && depth == 12) return conv_launch_t<WM, WN, MT, NT, 6, 12>(a, lds, s);
+    if constexpr (BM == 64 && BN == 64) {
+        if (kwt == 6 && depth == 4) return conv_launch_t<WM, WN, MT, NT, 6, 4>(a, lds, s);
+        if (kwt == 6 && depth == 12) return conv_launch_t<WM, WN, MT, NT, 6, 12>(a, lds, s);
     }
-    if (a.KW == 1 && depth == 4) return conv_launch_t<WM, WN, MT, NT, 1, 4>(a, lds, s);
-    return conv_launch_t<WM, WN, MT, NT, 0, 0>(a, lds, s);
+    if (kwt == 1 && depth == 4) return conv_launch_t<WM, WN, MT, NT, 1, 4>(a, lds, s);
+    if (kwt == 0 && depth == 0) return conv_launch_t<WM, WN, MT, NT, 0, 0>(a, lds, s);
+    return MCVC_ERR_INVALID;                       // a planned form that is not compiled
 }
 
 }  // namespace
@@ -511,6 +537,9 @@ static int conv_config(const Bf16ConvArgs& a)
 {
     static const int knob = mcvc_knob("MCVC_BF16_CFG", -1);
     if (a.Cout_pad % 64 != 0) return 2;
+    // a weight stage of 128 rows x KW taps must fit kMaxWP pieces per thread (KW <= 5); wider kernels -- the trunk's 1 x 6 fold once
+    // B * W4 > 8064 -- take the 64-row tiles, whatever the problem size
+    if (128 * a.KW * 4 > kMaxWP * kConvThreads) return 1;
     if (knob == 3 && a.stride == 2 && a.Cout_pad % 128 == 0 && !a.glu) return 3;
     const long long px = (long long)a.N * a.OH * a.OW;
     // 128 channels x 256 pixels: a workgroup streams its 128 x KH x KW x Cin weight slice once per PIXEL tile, and on the large stride-1
@@ -592,51 +621,72 @@ static double bf16_patch_conflicts(int tw_log2, int pw, int stride, int KH, int 
     return (double)extra / (double)n;
 }
 
-int mcvc_bf16_conv_launch(const Bf16ConvArgs& a0, hipStream_t s)
+// Everything the launch decides, on the host and without a HIP call (also behind mcvc_bf16_conv_plan / mcvc_gen_bf16_conv_plans of the C ABI)
+int mcvc_bf16_conv_make_plan(Bf16ConvArgs& a, Bf16ConvPlan& p)
 {
-    Bf16ConvArgs a = a0;
+    p = Bf16ConvPlan{};
+    p.cfg = -1;
     if ((a.Cin & 31) || (a.Cout & 3) || a.KW < 1 || a.KH < 1) return MCVC_ERR_INVALID;
     const int cfg = conv_config(a);
     const int BM = (cfg == 0 || cfg == 3 || cfg == 4 || cfg == 5) ? 128 : (cfg == 1 ? 64 : 32);
     const int BN = (cfg == 5) ? 512 : ((cfg == 4) ? 256 : ((cfg == 1 || cfg == 3) ? 64 : 128));
+    p.cfg = cfg; p.BM = BM; p.BN = BN;
     if (a.Cout_pad % BM) return MCVC_ERR_INVALID;
     if (a.glu && cfg != 0 && cfg != 4) return MCVC_ERR_INVALID;
+    if (BM * a.KW * 4 > kMaxWP * kConvThreads) return MCVC_ERR_INVALID;
+    a.TH = 0; a.tw_log2 = 0;
     mcvc_bf16_conv_tile(a.OH, a.OW, a.KH, a.KW, a.stride, BN, &a.TH, &a.tw_log2);
+    if (a.TH < 1) return MCVC_ERR_INVALID;                  // no tile shape whose staged patch fits
     const int TW = 1 << a.tw_log2;
     a.tiles_h = cdiv_i(a.OH, a.TH); a.tiles_w = cdiv_i(a.OW, TW);
     a.PH = (a.TH - 1) * a.stride + a.KH; a.PW = (TW - 1) * a.stride + a.KW;
+    p.TH = a.TH; p.TW = TW; p.tiles_h = a.tiles_h; p.tiles_w = a.tiles_w;
     {   // widen the staged patch to the nearest row pitch whose operand reads are free of LDS bank conflicts (the extra columns are
-        // real image columns or zero fill; nothing reads them)
+        // real image columns or zero fill; nothing reads them), as far as the two weight stages leave room: the 35-row patch of a 16 x 16
+        // stride-2 tile beside two 40 KB stages has 36 columns at most, and a wider pitch made downSample1 at 32 x 65 frames unlaunchable
         static const int knob = mcvc_knob("MCVC_BF16_PITCH", 1);
         if (knob && a.tw_log2 < 5) {
+            const size_t room = (size_t)160 * 1024 - 2 * (size_t)BM * a.KW * 64;
             int best = a.PW; double bc = bf16_patch_conflicts(a.tw_log2, a.PW, a.stride, a.KH, a.KW);
             for (int pw = a.PW + 1; pw <= a.PW + 12 && bc > 0.0; ++pw) {
-                if ((size_t)a.PH * pw * 64 > 96 * 1024) break;
+                if ((size_t)a.PH * pw * 64 > 96 * 1024 || (size_t)a.PH * pw * 64 > room) break;
                 const double c = bf16_patch_conflicts(a.tw_log2, pw, a.stride, a.KH, a.KW);
                 if (c < bc) { bc = c; best = pw; }
             }
             a.PW = best;
         }
     }
-    if (BM * a.KW * 4 > kMaxWP * kConvThreads) return MCVC_ERR_INVALID;
+    p.PH = a.PH; p.PW = a.PW;
+    p.xcd_map = conv_xcd_map(a.Cout_pad / BM, a.N * a.tiles_h * a.tiles_w) ? 1 : 0;
     // the patch area holds whole prefetch rounds (depth * 256 threads * 16 bytes): every thread stores every piece, no bounds test
     const int depth = bf16_prefetch_depth(a.PH * a.PW * 4, a.KW, BM, BN);
+    bf16_conv_form(a.KW, depth, BM, BN, &p.KWT, &p.PPT);
     size_t patch = ((size_t)a.PH * a.PW * 64 + 255) & ~(size_t)255;
     if (patch < (size_t)depth * 4096) patch = (size_t)depth * 4096;
     const size_t wb = (size_t)BM * a.KW * 64;
     a.patch_bytes = (int)patch;
     a.wbufs = 2;                    // weight stages alternate between two LDS buffers (DMA of the next one during the MFMAs)
     const size_t lds = patch + a.wbufs * wb;
+    p.lds_bytes = (int)(lds < ((size_t)1 << 30) ? lds : ((size_t)1 << 30));
     if (lds > 160 * 1024) return MCVC_ERR_INVALID;
+    return 0;
+}
+
+int mcvc_bf16_conv_launch(const Bf16ConvArgs& a0, hipStream_t s)
+{
+    Bf16ConvArgs a = a0;
+    Bf16ConvPlan p;
+    const int e = mcvc_bf16_conv_make_plan(a, p);
+    if (e) return e;
     const double px = (double)a.N * a.OH * a.OW;
     TraceScope ts(K_CONV_L, s, 2.0 * px * a.Cout_pad * a.Cin * a.KH * a.KW,
                   2.0 * ((double)a.N * a.H * a.W * a.Cin + px * a.Cout + (double)a.Cout_pad * a.Cin * a.KH * a.KW));
-    if (cfg == 0) return conv_launch_kw<2, 2, 2, 2>(a, lds, s);
-    if (cfg == 4) return conv_launch_kw<2, 2, 2, 4>(a, lds, s);
-    if (cfg == 5) return conv_launch_kw<1, 4, 4, 4>(a, lds, s);
-    if (cfg == 1) return conv_launch_kw<2, 2, 1, 1>(a, lds, s);
-    if (cfg == 3) return conv_launch_kw<2, 2, 2, 1>(a, lds, s);
-    return conv_launch_kw<1, 4, 1, 1>(a, lds, s);
+    if (p.cfg == 0) return conv_launch_kw<2, 2, 2, 2>(a, p, s);
+    if (p.cfg == 4) return conv_launch_kw<2, 2, 2, 4>(a, p, s);
+    if (p.cfg == 5) return conv_launch_kw<1, 4, 4, 4>(a, p, s);
+    if (p.cfg == 1) return conv_launch_kw<2, 2, 1, 1>(a, p, s);
+    if (p.cfg == 3) return conv_launch_kw<2, 2, 2, 1>(a, p, s);
+    return conv_launch_kw<1, 4, 1, 1>(a, p, s);
 }
 
 // ======================================================================================================================

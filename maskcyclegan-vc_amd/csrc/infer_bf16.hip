@@ -29,6 +29,7 @@ struct LayerB {
     int stride, pad_h, pad_w;
     int glu_fused;
     long long off_w, off_bias;     // byte offsets in the pack
+    int id;                        // layer id of the plan rows (include/mcvc.h, mcvc_gen_bf16_conv_plans)
 };
 
 struct NetB {
@@ -73,6 +74,8 @@ static NetB build_net()
     long long cur = 0;
     auto take = [&](long long bytes) { const long long o = cur; cur += (bytes + 255) & ~255LL; return o; };
     LayerB* all[] = {&n.conv1, &n.ds1, &n.ds2, &n.c2d1d, &n.c1d2d, &n.up1, &n.up2, &n.last};
+    for (int i = 0; i < 8; ++i) all[i]->id = i;
+    for (int i = 0; i < 6; ++i) { n.res_vg[i].id = 10 + i; n.res_out[i].id = 20 + i; }
     auto place = [&](LayerB& l) {
         l.off_w = take(2LL * l.Cout_pad * l.KH * l.Cin * l.KW);
         l.off_bias = take(4LL * l.Cout_pad);
@@ -128,22 +131,47 @@ struct Run {
     const unsigned char* pk;
     unsigned char* ws;
     const Work* w;
+    // plan-only mode (mcvc_gen_bf16_conv_plans): forward() walks the same schedule, every generic conv() appends its row
+    // {layer id, plan} instead of launching, and nothing else is launched -- no device pointer is formed or read
+    bool plan; int* rows; int cap, n_rows;
     void fail(int e) { if (!err && e) err = e; }
 };
+constexpr int kPlanFields = 13, kPlanRow = 1 + kPlanFields;
+static const float* const kNoParams[110] = {};             // the parameter table of a plan-only run
+
+static void plan_fields(const Bf16ConvPlan& p, int* out)
+{
+    const int f[kPlanFields] = {p.cfg, p.BM, p.BN, p.KWT, p.PPT, p.TH, p.TW, p.tiles_h, p.tiles_w, p.PH, p.PW, p.lds_bytes, p.xcd_map};
+    for (int i = 0; i < kPlanFields; ++i) out[i] = f[i];
+}
+
+// the problem a layer's conv() call poses to the launcher (everything but the pointers and strides)
+static Bf16ConvArgs conv_problem(const LayerB& l, int N, int H, int W, int Cout_store)
+{
+    Bf16ConvArgs a{};
+    a.N = N; a.H = H; a.W = W; a.Cin = l.Cin; a.Cout = Cout_store; a.Cout_pad = l.Cout_pad;
+    a.KH = l.KH; a.KW = l.KW; a.stride = l.stride; a.pad_h = l.pad_h; a.pad_w = l.pad_w;
+    a.OH = conv_out(H, l.KH, l.stride, l.pad_h); a.OW = conv_out(W, l.KW, l.stride, l.pad_w);
+    a.glu = l.glu_fused;
+    return a;
+}
 
 // y[n][oh][ow][co] = conv(x) (+bias)
 static void conv(Run& r, const LayerB& l, const bf16_t* x, long long x_sn, int x_sh, int x_sw, int N, int H, int W, bf16_t* y, long long y_sn,
                  int y_sh, int y_sw, int Cout_store)
 {
-    Bf16ConvArgs a{};
+    Bf16ConvArgs a = conv_problem(l, N, H, W, Cout_store);
+    if (r.plan) {
+        Bf16ConvPlan p;
+        r.fail(mcvc_bf16_conv_make_plan(a, p));
+        if (r.n_rows < r.cap) { r.rows[r.n_rows * kPlanRow] = l.id; plan_fields(p, r.rows + r.n_rows * kPlanRow + 1); }
+        ++r.n_rows;
+        return;
+    }
     a.x = x; a.x_sn = x_sn; a.x_sh = x_sh; a.x_sw = x_sw;
     a.w = reinterpret_cast<const bf16_t*>(r.pk + l.off_w);
     a.bias = reinterpret_cast<const float*>(r.pk + l.off_bias);
     a.y = y; a.y_sn = y_sn; a.y_sh = y_sh; a.y_sw = y_sw;
-    a.N = N; a.H = H; a.W = W; a.Cin = l.Cin; a.Cout = Cout_store; a.Cout_pad = l.Cout_pad;
-    a.KH = l.KH; a.KW = l.KW; a.stride = l.stride; a.pad_h = l.pad_h; a.pad_w = l.pad_w;
-    a.OH = conv_out(H, l.KH, l.stride, l.pad_h); a.OW = conv_out(W, l.KW, l.stride, l.pad_w);
-    a.glu = l.glu_fused;
     r.fail(mcvc_bf16_conv_launch(a, r.s));
 }
 
@@ -151,6 +179,7 @@ static void norm(Run& r, const bf16_t* x, long long x_sn, int x_sh, int x_sw, in
                  const float* g0, const float* b0, const float* g1, const float* b1, const bf16_t* res, bf16_t* y, long long y_sn, int y_sh,
                  int y_sw, int y_csplit = 0, int y_sc2 = 0)
 {
+    if (r.plan) return;
     Bf16NormArgs a{};
     a.x = x; a.x_sn = x_sn; a.x_sh = x_sh; a.x_sw = x_sw; a.N = N; a.H = H; a.W = W; a.Cx = Cx;
     a.shuffle = shuffle; a.act = act; a.has_norm = 1;
@@ -167,17 +196,19 @@ static void forward(Run& r, const float* x, const float* mask, float* out, const
     const NetB& n = net();
     const Work& w = *r.w;
     const float* const* P = r.P;
-    auto B16 = [&](long long off) { return reinterpret_cast<bf16_t*>(r.ws + off); };
+    auto B16 = [&](long long off) { return r.plan ? nullptr : reinterpret_cast<bf16_t*>(r.ws + off); };
+    auto PKW = [&](long long off) { return r.plan ? nullptr : reinterpret_cast<const bf16_t*>(r.pk + off); };
+    auto PKF = [&](long long off) { return r.plan ? nullptr : reinterpret_cast<const float*>(r.pk + off); };
     const int B = d.B, T = d.T, W2 = d.W2, W4 = d.W4, Wu1 = d.Wu1, Wu2 = d.Wu2;
     // model.py:241-242: stack(x*mask, mask), the 15 kernel columns folded into the channel axis; gated 5x15 conv, GLU in the epilogue
     // (r6: one launch -- the folded tensor is built in LDS, the weights live in registers; MCVC_BF16_CONV1_FUSED=0 in the experiments build
     //  restores input-prep kernel + generic tile for the A/B)
     static const int c1_fused = mcvc_knob("MCVC_BF16_CONV1_FUSED", 1);
     if (c1_fused) {
-        r.fail(mcvc_bf16_conv1_fused_launch(x, mask, reinterpret_cast<const bf16_t*>(r.pk + n.conv1.off_w), reinterpret_cast<const float*>(r.pk + n.conv1.off_bias),
-                                            B16(w.y1), B, 80, T, r.s));
+        if (!r.plan) r.fail(mcvc_bf16_conv1_fused_launch(x, mask, PKW(n.conv1.off_w), PKF(n.conv1.off_bias),
+                                                         B16(w.y1), B, 80, T, r.s));
     } else {
-        r.fail(mcvc_bf16_prep_launch(x, mask, B16(w.xin), B, 80, T, r.s));
+        if (!r.plan) r.fail(mcvc_bf16_prep_launch(x, mask, B16(w.xin), B, 80, T, r.s));
         conv(r, n.conv1, B16(w.xin), 80LL * T * 32, T * 32, 32, B, 80, T, B16(w.y1), 80LL * T * 128, T * 128, 128, 128);
     }
     // :245 downSample1
@@ -195,8 +226,8 @@ static void forward(Run& r, const float* x, const float* mask, float* out, const
     // experiments build restores the two-launch form
     static const int c2_fused = mcvc_knob("MCVC_BF16_C2D1D_FUSED", 1);
     if (c2_fused && mcvc_bf16_c2d1d_applies(W4)) {
-        r.fail(mcvc_bf16_c2d1d_launch(B16(w.y3), (long long)W4 * 5120, reinterpret_cast<const bf16_t*>(r.pk + n.off_c2), P[22], P[23], B16(w.h[0]),
-                                      (long long)W4 * 256, B, W4, kEps, r.s));
+        if (!r.plan) r.fail(mcvc_bf16_c2d1d_launch(B16(w.y3), (long long)W4 * 5120, PKW(n.off_c2), P[22], P[23], B16(w.h[0]),
+                                                   (long long)W4 * 256, B, W4, kEps, r.s));
     } else {
         conv(r, n.c2d1d, B16(w.y3), (long long)W4 * 5120, 0, 1024, B, 1, 5 * W4, B16(w.c4), (long long)W4 * 256, 0, 256, 256);
         norm(r, B16(w.c4), (long long)W4 * 256, 0, 256, B, 1, W4, 256, 0, BF16_ACT_NONE, P[22], P[23], nullptr, nullptr, nullptr,
@@ -210,10 +241,10 @@ static void forward(Run& r, const float* x, const float* mask, float* out, const
     const bool fused = trunk_fused && mcvc_bf16_trunk_layer_applies(W4, 256, 512) && mcvc_bf16_trunk_layer_applies(W4, 512, 256);
     for (int i = 0; i < 6 && fused; ++i) {
         const int b = 24 + 12 * i;
-        r.fail(mcvc_bf16_trunk_layer_launch(B16(w.h[cur]), (long long)W4 * 256, reinterpret_cast<const bf16_t*>(r.pk + n.off_tvg[i]), P[b + 2], P[b + 3], P[b + 6],
-                                            P[b + 7], nullptr, B16(w.ya), (long long)W4 * 512, B, W4, 256, 512, 1, kEps, r.s));
-        r.fail(mcvc_bf16_trunk_layer_launch(B16(w.ya), (long long)W4 * 512, reinterpret_cast<const bf16_t*>(r.pk + n.off_tout[i]), P[b + 10], P[b + 11], nullptr,
-                                            nullptr, B16(w.h[cur]), B16(w.h[cur ^ 1]), (long long)W4 * 256, B, W4, 512, 256, 0, kEps, r.s));
+        if (!r.plan) r.fail(mcvc_bf16_trunk_layer_launch(B16(w.h[cur]), (long long)W4 * 256, PKW(n.off_tvg[i]), P[b + 2], P[b + 3], P[b + 6],
+                                                         P[b + 7], nullptr, B16(w.ya), (long long)W4 * 512, B, W4, 256, 512, 1, kEps, r.s));
+        if (!r.plan) r.fail(mcvc_bf16_trunk_layer_launch(B16(w.ya), (long long)W4 * 512, PKW(n.off_tout[i]), P[b + 10], P[b + 11], nullptr,
+                                                         nullptr, B16(w.h[cur]), B16(w.h[cur ^ 1]), (long long)W4 * 256, B, W4, 512, 256, 0, kEps, r.s));
         cur ^= 1;
     }
     for (int i = 0; i < 6 && !fused; ++i) {
@@ -229,8 +260,8 @@ static void forward(Run& r, const float* x, const float* mask, float* out, const
     }
     // :266-271 1x1 256 -> 5120 (rows h*256 + c) + IN, written NHWC [b][h][w][c]
     conv(r, n.c1d2d, B16(w.h[cur]), (long long)W4 * 256, 0, 256, B, 1, W4, B16(w.c6), (long long)W4 * 5120, 0, 5120, 5120);
-    norm(r, B16(w.c6), (long long)W4 * 5120, 0, 5120, B, 1, W4, 5120, 0, BF16_ACT_NONE, reinterpret_cast<const float*>(r.pk + n.off_g6),
-         reinterpret_cast<const float*>(r.pk + n.off_b6), nullptr, nullptr, nullptr, B16(w.y6), 20LL * W4 * 256, 0, 256, 256, W4 * 256);
+    norm(r, B16(w.c6), (long long)W4 * 5120, 0, 5120, B, 1, W4, 5120, 0, BF16_ACT_NONE, PKF(n.off_g6),
+         PKF(n.off_b6), nullptr, nullptr, nullptr, B16(w.y6), 20LL * W4 * 256, 0, 256, 256, W4 * 256);
     // :274 upSample1: conv -> PixelShuffle -> IN -> x*sigmoid(x)
     conv(r, n.up1, B16(w.y6), 20LL * W4 * 256, W4 * 256, 256, B, 20, W4, B16(w.c7), 20LL * W4 * 1024, W4 * 1024, 1024, 1024);
     norm(r, B16(w.c7), 20LL * W4 * 1024, W4 * 1024, 1024, B, 20, W4, 1024, 1, BF16_ACT_SILU, P[106], P[107], nullptr, nullptr, nullptr,
@@ -243,10 +274,10 @@ static void forward(Run& r, const float* x, const float* mask, float* out, const
     // (r6: one launch, fp32 kernel-column sum in LDS; MCVC_BF16_LAST_FUSED=0 in the experiments build restores conv + shifted-plane sum)
     static const int last_fused = mcvc_knob("MCVC_BF16_LAST_FUSED", 1);
     if (last_fused) {
-        r.fail(mcvc_bf16_last_fused_launch(B16(w.y8), reinterpret_cast<const bf16_t*>(r.pk + n.last.off_w), P[109], out, B, 80, Wu2, r.s));
+        if (!r.plan) r.fail(mcvc_bf16_last_fused_launch(B16(w.y8), PKW(n.last.off_w), P[109], out, B, 80, Wu2, r.s));
     } else {
         conv(r, n.last, B16(w.y8), 80LL * Wu2 * 128, Wu2 * 128, 128, B, 80, Wu2, B16(w.z), 80LL * Wu2 * 32, Wu2 * 32, 32, 32);
-        r.fail(mcvc_bf16_last_launch(B16(w.z), P[109], out, B, 80, Wu2, r.s));
+        if (!r.plan) r.fail(mcvc_bf16_last_launch(B16(w.z), P[109], out, B, 80, Wu2, r.s));
     }
 }
 
@@ -312,20 +343,54 @@ int mcvc_gen_infer_bf16(const float* const* params, const void* packed, const fl
     return r.err;
 }
 
+// Host only: the plan row {layer id, 13 plan fields} of every generic conv() call the forward above makes for (B, T), in call order --
+// the same forward() in plan-only mode, so the fused / unfused branches are taken exactly as a real run takes them.
+int mcvc_gen_bf16_conv_plans(int B, int T, int* rows, int cap, int* n)
+{
+    if (B < 1 || T < 1 || !n || cap < 0 || (cap > 0 && !rows)) return MCVC_ERR_INVALID;
+    const Dims d = dims(B, T);
+    if (d.W4 < 2) return MCVC_ERR_INVALID;
+    const Work w = work(d);
+    Run r{}; r.P = kNoParams; r.w = &w; r.plan = true; r.rows = rows; r.cap = cap;
+    forward(r, nullptr, nullptr, nullptr, d);
+    *n = r.n_rows;
+    if (r.err) return r.err;
+    return r.n_rows > cap ? MCVC_ERR_WORKSPACE : 0;
+}
+
 // ---- single-op entry points (kernel parity tests; same kernels the forward uses) -----------------------------------------------
 // y[N][OH][OW][Cout] (bf16 NHWC) = conv2d(x[N][H][W][Cin] bf16 NHWC, w[Cout][Cin][KH][KW] fp32 OIHW -> bf16) + bias
+static int conv2d_cout_pad(int Cout) { return (Cout % 128 == 0) ? Cout : ((Cout + 31) / 32) * 32; }
+static LayerB conv2d_layer(int Cin, int Cout, int KH, int KW, int stride, int pad_h, int pad_w)
+{
+    return mkl(BF16_PACK_PLAIN, 0, 1, -1, -1, Cout, Cin, KH, KW, Cin, KW, conv2d_cout_pad(Cout), stride, pad_h, pad_w);
+}
+
 long long mcvc_bf16_conv2d_pack_bytes(int Cout, int Cin, int KH, int KW)
 {
-    const int cout_pad = (Cout % 128 == 0) ? Cout : ((Cout + 31) / 32) * 32;
+    const int cout_pad = conv2d_cout_pad(Cout);
     return 2LL * cout_pad * KH * Cin * KW + 4LL * cout_pad + 512;
+}
+
+// Host only: the plan mcvc_bf16_conv2d's launch would run for this problem, and the launch's return value
+int mcvc_bf16_conv_plan(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_h, int pad_w, int* out, int n_out)
+{
+    if (!out || n_out < kPlanFields || N < 1 || stride < 1) return MCVC_ERR_INVALID;
+    for (int i = 0; i < n_out; ++i) out[i] = 0;
+    if ((Cin & 31) || (Cout & 3)) return MCVC_ERR_INVALID;
+    Bf16ConvArgs a = conv_problem(conv2d_layer(Cin, Cout, KH, KW, stride, pad_h, pad_w), N, H, W, Cout);
+    Bf16ConvPlan p;
+    const int e = mcvc_bf16_conv_make_plan(a, p);
+    plan_fields(p, out);
+    return e;
 }
 
 int mcvc_bf16_conv2d(const void* x, const float* w, const float* bias, void* y, void* wpack, int N, int H, int W, int Cin, int Cout,
                      int KH, int KW, int stride, int pad_h, int pad_w, void* stream)
 {
     if ((Cin & 31) || (Cout & 3) || !x || !w || !y || !wpack) return MCVC_ERR_INVALID;
-    const int cout_pad = (Cout % 128 == 0) ? Cout : ((Cout + 31) / 32) * 32;
-    LayerB l = mkl(BF16_PACK_PLAIN, 0, 1, -1, -1, Cout, Cin, KH, KW, Cin, KW, cout_pad, stride, pad_h, pad_w);
+    const int cout_pad = conv2d_cout_pad(Cout);
+    LayerB l = conv2d_layer(Cin, Cout, KH, KW, stride, pad_h, pad_w);
     l.off_w = 0; l.off_bias = ((2LL * cout_pad * KH * Cin * KW) + 255) & ~255LL;
     const float* P[2] = {w, bias};
     Run r{}; r.s = (hipStream_t)stream; r.P = P; r.pk = static_cast<const unsigned char*>(wpack);

@@ -72,6 +72,8 @@ _SIGS = {
     "mcvc_gen_infer_bf16": (c_int, [_PP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p]),
     "mcvc_bf16_conv2d_pack_bytes": (c_longlong, [c_int, c_int, c_int, c_int]),
     "mcvc_bf16_conv2d": (c_int, [c_void_p] * 5 + [c_int] * 10 + [c_void_p]),
+    "mcvc_bf16_conv_plan": (c_int, [c_int] * 10 + [c_void_p, c_int]),                  # host only
+    "mcvc_gen_bf16_conv_plans": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p]),     # host only
     "mcvc_bf16_instnorm_act": (c_int, [c_void_p] * 8 + [c_int] * 6 + [c_void_p]),
     "mcvc_bf16_c2d1d_pack_bytes": (c_longlong, []),
     "mcvc_bf16_c2d1d_norm": (c_int, [c_void_p] * 6 + [c_int] * 2 + [c_void_p]),
