@@ -20,10 +20,11 @@ from __future__ import annotations
 
 import ctypes
 import os
+from types import SimpleNamespace
 
 import torch
 
-from . import _hip
+from . import _hip, step_graphs
 from ._hip import check, lib, ptr, ptr_table, stream
 from .lanes import get_lanes
 from .optim_state import load_optimizer_state_dict, optimizer_state_dict
@@ -319,18 +320,18 @@ class TrainEngine:
         names = list(names)
         while names:
             grp, names = names[:4], names[4:]
-            self._run_tasks([(i, (lambda ln, n=n: self._repack1(n)), (), None) for i, n in enumerate(grp)])
+            self._run_tasks([(i, n, (), None) for i, n in enumerate(grp)], {n: (lambda ln, n=n: self._repack1(n)) for n in grp})
 
-    def _run_tasks(self, tasks):
+    def _run_tasks(self, tasks, parts):
         """Submit a phase as a dependency graph instead of fork/join rounds.
 
-        ``tasks`` is a list of ``(lane, fn, waits, record)`` in a valid topological order: ``fn(lane)`` is queued on lane ``lane``'s HIP
-        stream (lane 0 = the caller's stream) after the events named in ``waits``; ``record`` names the event recorded behind it.  Work of
-        one lane is ordered by its stream, cross-lane edges are events, everything joins the caller's stream at the end.  Serial mode runs
-        the same list in order on one stream."""
+        ``tasks`` is a list of ``(lane, part_name, waits, record)`` in a valid topological order (step_graphs.py): ``parts[part_name](lane)``
+        is queued on lane ``lane``'s HIP stream (lane 0 = the caller's stream) after the events named in ``waits``; ``record`` names the
+        event recorded behind it.  Work of one lane is ordered by its stream, cross-lane edges are events, everything joins the caller's
+        stream at the end.  Serial mode runs the same list in order on one stream."""
         if not self.concurrent or self._serial:
-            for lane, fn, _, _ in tasks:
-                fn(lane)
+            for lane, name, _, _ in tasks:
+                parts[name](lane)
             return
         main = torch.cuda.current_stream(self.device)
         streams = [main] + self._sides
@@ -338,8 +339,8 @@ class TrainEngine:
         for ln in used:
             streams[ln].wait_stream(main)
         done = {}
-        for ti, (lane, fn, waits, rec) in enumerate(tasks):
-            st = streams[lane]
+        for ti, (lane, name, waits, rec) in enumerate(tasks):
+            st, fn = streams[lane], parts[name]
             with torch.cuda.stream(st):
                 for w in waits:
                     st.wait_event(done[w])
@@ -348,7 +349,7 @@ class TrainEngine:
                     e0.record(st)
                     fn(lane)
                     e1.record(st)
-                    self._timeline.append((ti, lane, "%s:%s" % (getattr(fn, "__name__", "?"), rec), waits, e0, e1))
+                    self._timeline.append((ti, lane, "%s:%s" % (name, rec), waits, e0, e1))
                 else:
                     fn(lane)
                 if rec is not None:
@@ -430,10 +431,11 @@ class TrainEngine:
         check(self.L.mcvc_disc_forward(self._p_tab[name], ptr(self.packed[name]), ptr(x), ptr(out), ptr(stash), ptr(sc), sc.numel(), nb, self.T, stream()),
               "disc_forward")
 
-    def _D_bwd(self, name, dlogit, dx, acc, stash, with_weight_grads, nb, lane=0, aux_stream=None, store=False):
+    def _D_bwd(self, name, dlogit, dx, acc, stash, with_weight_grads, nb, lane=0, aux_stream=None, aux_lane=None, store=False):
+        """``lane`` picks the scratch buffer (the network's index) and, unless ``aux_lane`` names another, the auxiliary stream."""
         sc = self.d_scratch[lane]
         aux = ctypes.c_void_p(aux_stream.cuda_stream) if (aux_stream is not None and with_weight_grads and self.aux_wgrad) else \
-            (self._aux_ptr(lane) if (with_weight_grads and self.aux_wgrad_d) else None)
+            (self._aux_ptr(lane if aux_lane is None else aux_lane) if (with_weight_grads and self.aux_wgrad_d) else None)
         check(self.L.mcvc_disc_backward_flags(self._p_tab[name], ptr(self.packed[name]), self._g_tab[name] if with_weight_grads else None, ptr(dlogit), 1,
                                               ptr(dx), acc, ptr(stash), ptr(sc), sc.numel(), nb, self.T, stream(), aux,
                                               4 if (store and with_weight_grads) else 0), "disc_backward")
@@ -494,136 +496,94 @@ class TrainEngine:
         st = self.g_group.step
         self._twin(lambda: self._update_gen(G_NAMES[0], 7, lr, st, zero), lambda: self._update_gen(G_NAMES[1], 7, lr, st, zero))
 
-    # ---- the two phases -------------------------------------------------------------------------------
-    def generator_phase(self, real_A, mask_A, real_B, mask_B, fuse_update=False):
-        """train.py:195-242 on four lanes (more than ``grouped_max_b`` samples per pass).  ``fuse_update`` (what ``step()`` uses): each lane
-        also runs the optimizer step of the generator whose last backward pass it ran, fused with the refresh of its packed copies
-        (train.py:242) -- no join of the lanes, one launch per generator."""
-        B, B2 = self.B, 2 * self.B
-        m = self.mel
-        sc = self.sched
-        self.slots[:_BLOCK].zero_()
-        self._take_grads("g")                    # (usually clean: zeroed on an idle lane during the previous discriminator phase)
-        # batched inputs (device-to-device copies; the batch dimension is outermost, so halves are contiguous views)
-        torch._foreach_copy_([self.in_A2B[:B], self.in_A2B[B:], self.in_B2A[:B], self.in_B2A[B:], self.mask_A2B[:B], self.mask_B2A[:B]],
-                             [real_A, real_B, real_B, real_A, mask_A, mask_B])     # one launch; the masks' second halves stay all-ones
-        fake_B, identity_B = self.out_A2B[:B], self.out_A2B[B:]
-        fake_A, identity_A = self.out_B2A[:B], self.out_B2A[B:]
-        g_fake_B, g_identity_B = self.gout_A2B[:B], self.gout_A2B[B:]
-        g_fake_A, g_identity_A = self.gout_B2A[:B], self.gout_B2A[B:]
-        do, dl, ds = self.dout1, self.dlogit1, self.d_stash1
-        # The phase as a dependency graph over four lanes.  Lane 0 follows real_A -> fake_B -> cycle_A -> D_A2 and back, lane 1 follows
-        # real_B -> fake_A -> cycle_B -> D_B2 and back: these two are the critical path.  The first-step adversarial terms D_A(fake_A),
-        # D_B(fake_B) need only the translated batches: lanes 2 and 3 run their forward, loss and data-gradient WHILE lanes 0/1 are in the
-        # cycle forwards.  Cross-lane edges: the translated batches (g0, g1), the adversarial gradients that the cycle backward accumulates
-        # onto (dA, dB), and the two backward passes of one generator, which accumulate into the same weight gradients (c0, c1).
-        cl, il = sc.cycle_loss_lambda, sc.identity_loss_lambda
-        # After the identity cut-off (train.py:314-315: lambda = 0 for the rest of training, 98 % of a default run) the identity passes are
-        # dead code -- their loss term weighs 0 and so does every gradient behind it; like the discriminators' weight gradients of this
-        # phase they are not computed: the translation passes run over B samples instead of 2B.
-        nbt = B2 if il != 0 else B
-
-        def cycle_a(ln):
-            self._G("generator_B2A", fake_B, None, m["cycle_A"], self.g_stash1[0], B, ln)                  # :204 (mask of ones)
-            self._l1(m["cycle_A"], real_A, cl, m["g_cycle_A"], 0)                                          # :219
-            if il != 0:
-                self._l1(identity_B, real_B, il, g_identity_B, 3)                                          # :224
-
-        def cycle_b(ln):
-            self._G("generator_A2B", fake_A, None, m["cycle_B"], self.g_stash1[1], B, ln)                  # :206
-            self._l1(m["cycle_B"], real_B, cl, m["g_cycle_B"], 1)                                          # :220
-            if il != 0:
-                self._l1(identity_A, real_A, il, g_identity_A, 2)                                          # :223
-
-        def adv(name, i, x, gx, acc):
-            def run(ln):
-                self._D(name, x, do[i], ds[i], B, ln)                                                      # :211-216
-                self._lsgan(do[i], 1.0, 1.0, 4 + i, dl[i])                                                 # :227-231
-                self._D_bwd(name, dl[i], gx, acc, ds[i], False, B, ln)         # discriminators contribute data-gradients only
-            return run
-
-        def finish_d(ln):                      # data parallel: the D gradient all-reduce of the previous iteration runs behind the
-            self._finish_d_update()            # generator forwards; lane 2 is the first to need the discriminators
-            if fuse_update:
-                # the discriminator gradients are free once their Adam step is queued: clear them here, on an idle lane, instead of
-                # on the caller's stream at the top of the discriminator phase (99 MB memset)
-                self._clear_grads("d")
-        ov = self.overlap_g_reduce
-        if fuse_update:
-            self.g_group.step += 1
-        g_step, g_lr = self.g_group.step, sc.g_opt_lr
-
-        def queue_reduce(ln):
-            # data parallel: the generator gradients are exchanged range by range BEHIND the last backward passes (their milestone events;
-            # the tails behind the passes themselves), on the communication stream, in the same order on every rank
-            for k in range(2):
-                for n in G_NAMES:
-                    lo, hi = self._g_ranges[n][k]
-                    self.reducer.reduce_range_after_(self.g_group.grad, lo, hi, self._ms[n][0][k])
-            for n, ev in zip(G_NAMES, ("fA2B", "fB2A")):
-                lo, hi = self._g_ranges[n][2]
-                # serial mode records no task events (one stream: everything queued so far is the dependency); a stale event of an
-                # earlier concurrent iteration must not be used either
-                self.reducer.reduce_range_after_(self.g_group.grad, lo, hi, self._task_events.get(ev) if self.concurrent else None)
-
-        def update(name):
-            def run(ln):
-                self.reducer.wait(self.device)             # (no-op on one GPU)
-                self._update_gen(name, 7, g_lr, g_step, zero=False)
-            return run
-        assert G_NAMES[0] == "generator_A2B"
-        self._run_tasks([
-            (0, lambda ln: self._G("generator_A2B", self.in_A2B, self.mask_A2B, self.out_A2B, self.g_stash2[0], nbt, ln), (), "g0"),   # :203, :209-210
-            (1, lambda ln: self._G("generator_B2A", self.in_B2A, self.mask_B2A, self.out_B2A, self.g_stash2[1], nbt, ln), (), "g1"),   # :205, :207-208
-            (0, cycle_a, (), None),
-            (1, cycle_b, (), None),
-            (2, finish_d, (), None),
-            (2, adv("discriminator_A", 0, fake_A, g_fake_A, 0), ("g1",), "dA"),
-            (3, adv("discriminator_B", 1, fake_B, g_fake_B, 0), ("g0",), "dB"),
-            (0, adv("discriminator_A2", 2, m["cycle_A"], m["g_cycle_A"], 1), (), None),
-            (1, adv("discriminator_B2", 3, m["cycle_B"], m["g_cycle_B"], 1), (), None),
-            # backward through the cycle passes: cycle_A = G_B2A(fake_B) adds to d(fake_B), cycle_B = G_A2B(fake_A) to d(fake_A)
-            (0, lambda ln: self._G_bwd("generator_B2A", None, m["g_cycle_A"], g_fake_B, 1, self.g_stash1[0], B, ln), ("dB",), "c0"),
-            (1, lambda ln: self._G_bwd("generator_A2B", None, m["g_cycle_B"], g_fake_A, 1, self.g_stash1[1], B, ln), ("dA",), "c1"),
-            # the last pass over each generator: its gradient ranges become final one after the other (milestone events)
-            (0, lambda ln: self._G_bwd("generator_A2B", self.mask_A2B, self.gout_A2B, None, 0, self.g_stash2[0], nbt, ln, ov), ("c1",), "fA2B"),
-            (1, lambda ln: self._G_bwd("generator_B2A", self.mask_B2A, self.gout_B2A, None, 0, self.g_stash2[1], nbt, ln, ov), ("c0",), "fB2A"),
-        ] + ([(2, queue_reduce, (), None)] if (fuse_update and ov) else [])
-          + ([(0, update("generator_A2B"), (), None), (1, update("generator_B2A"), (), None)] if fuse_update else []))
-        self._g_fwd_packed = bool(fuse_update)
-        self._combine(0, self._comb_g)          # g_loss and its terms, summed in the reference's order (:233-237)
-
     def _use_grouped(self):
         return self.grouped and self.B <= self.grouped_max_b
 
-    # ---- grouped schedule: the two phases as parts that the plain and the pipelined step assemble into task graphs ----------------
-    def _g_parts(self, inp, fuse_update, own_d_update=True, zeroing_update=False, ranged=False, can_store=True):
-        """Closures of the generator phase (train.py:195-242) in grouped launches.  ``own_d_update``: the first-step adversarial pair
-        completes a deferred discriminator update itself (plain step); the pipelined step orders the discriminators' update in front of
-        the adversarial pairs through the task graph instead.  ``zeroing_update``: zero_grads mode of the update (0 / 1 / 2); ``can_store``:
-        the cycle backward -- the first weight-gradient pass over both generators -- may store into a store-ready buffer (``take``)."""
+    # ---- the two phases as parts: every body of the step's dataflow exists once here; the schedules are graphs over them (step_graphs.py) ----
+    def _emit(self, P, laned, name, f):
+        """One part with an A- and a B-direction, ``f(k, slot)`` with k = 0 / 1 the direction.  Grouped: ONE task ``name`` that runs both
+        directions as one set of grouped launches.  Laned: two tasks ``name_A`` / ``name_B``; ``slot`` is the lane the task runs on."""
+        if laned:
+            P[name + "_A"], P[name + "_B"] = (lambda ln: f(0, ln)), (lambda ln: f(1, ln))
+        else:
+            P[name] = lambda ln: self._twin(lambda: f(0, 0), lambda: f(1, 1))
+
+    def _bind_plain(self, inp):
+        """Where the generator phase's tensors live when it runs its own passes: direction k = 0 is real_A -> fake_B -> cycle_A, k = 1 is
+        real_B -> fake_A -> cycle_B; generator k runs [translation ; identity] in one pass, then the cycle pass of the other direction."""
         real_A, mask_A, real_B, mask_B = inp
+        B = self.B
+        # After the identity cut-off (train.py:314-315: lambda = 0 for the rest of training, 98 % of a default run) the identity passes are
+        # dead code -- their loss term weighs 0 and so does every gradient behind it; like the discriminators' weight gradients of this
+        # phase they are not computed: the translation passes run over B samples instead of 2B (the halves of the batched buffers are
+        # contiguous: translation first, identity second).
+        nbt = 2 * B if self.sched.identity_loss_lambda != 0 else B
+        out, gout = (self.out_A2B, self.out_B2A), (self.gout_A2B, self.gout_B2A)
+        cyc = (self.mel["cycle_A"], self.mel["cycle_B"])
+        fake = (out[0][:B], out[1][:B])
+        return SimpleNamespace(
+            real=(real_A, real_B),
+            # batched inputs (device-to-device copies; the batch dimension is outermost, so halves are contiguous views)
+            copies=([self.in_A2B[:B], self.in_A2B[B:], self.in_B2A[:B], self.in_B2A[B:], self.mask_A2B[:B], self.mask_B2A[:B]],
+                    [real_A, real_B, real_B, real_A, mask_A, mask_B]),                 # (the masks' second halves stay all-ones)
+            fwd=((self.in_A2B, self.mask_A2B, out[0], self.g_stash2[0]), (self.in_B2A, self.mask_B2A, out[1], self.g_stash2[1])),
+            nb_fwd=nbt, nb_bwd=nbt, fake=fake, ident=(out[0][B:], out[1][B:]), gout=gout,
+            g_fake=(gout[0][:B], gout[1][:B]), g_ident=(gout[0][B:], gout[1][B:]),
+            cyc_in=fake, cyc_out=cyc, cycle=cyc, cyc_stash=self.g_stash1, nb_cyc=B,
+            no_join=False, sc_final=(0, 1), merged=False)
+
+    def _bind_merged(self, cur, prev):
+        """... and when the previous iteration's discriminator phase rides in its passes (_merged_step): one pass per generator carries
+        [identity | translation | D-phase translation of ``prev``], the cycle pass [cycle | D-phase cycle]; the backward passes run over
+        a window of those stashes.  ``prev`` None (first iteration): a throw-away third sample."""
+        real_A, mask_A, real_B, mask_B = cur
+        p_real_A, p_mask_A, p_real_B, p_mask_B = prev if prev is not None else cur
         B, B2 = self.B, 2 * self.B
-        m = self.mel
-        sc = self.sched
-        fake_B, identity_B = self.out_A2B[:B], self.out_A2B[B:]
-        fake_A, identity_A = self.out_B2A[:B], self.out_B2A[B:]
-        g_fake_B, g_identity_B = self.gout_A2B[:B], self.gout_A2B[B:]
-        g_fake_A, g_identity_A = self.gout_B2A[:B], self.gout_B2A[B:]
-        do, dl, ds = self.dout1, self.dlogit1, self.d_stash1
-        cl, il = sc.cycle_loss_lambda, sc.identity_loss_lambda
         A2B, B2A = G_NAMES
+        in3, mask3, out3, gout3, di = self.in3, self.mask3, self.out3, self.gout3, self.d_in
+        out, gout, cyc2 = (out3[A2B], out3[B2A]), (gout3[A2B], gout3[B2A]), (self.cyc2["A"], self.cyc2["B"])
+        return SimpleNamespace(
+            real=(real_A, real_B),
+            copies=([in3[A2B][:B], in3[A2B][B:B2], in3[A2B][B2:], mask3[A2B][B:B2], mask3[A2B][B2:],
+                     in3[B2A][:B], in3[B2A][B:B2], in3[B2A][B2:], mask3[B2A][B:B2], mask3[B2A][B2:]],
+                    [real_B, real_A, p_real_A, mask_A, p_mask_A,
+                     real_A, real_B, p_real_B, mask_B, p_mask_B]),                     # (the identity samples' masks stay all-ones)
+            fwd=((in3[A2B], mask3[A2B], out[0], self.g_stash3x[0]), (in3[B2A], mask3[B2A], out[1], self.g_stash3x[1])),
+            nb_fwd=3 * B, nb_bwd=B2, fake=(out[0][B:B2], out[1][B:B2]), ident=(out[0][:B], out[1][:B]), gout=gout,
+            g_fake=(gout[0][B:], gout[1][B:]), g_ident=(gout[0][:B], gout[1][:B]),
+            cyc_in=(out[0][B:], out[1][B:]), cyc_out=cyc2, cycle=(cyc2[0][:B], cyc2[1][:B]), cyc_stash=self.g_stash2c, nb_cyc=B2,
+            # The cycle pass's weight gradients (auxiliary stream) outlast its data-gradient chain by ~0.2 ms; the translation pass needs only
+            # the data gradient, so it starts without that join (MCVC_BWD_NO_JOIN, include/mcvc.h): its own weight gradients queue behind them
+            # on the same auxiliary stream (same tensors, in order), it works in other scratch buffers (4, 5), and its final join covers both.
+            no_join=True, sc_final=(4, 5), merged=True,
+            repack=not self._g_fwd_packed,
+            # the D-phase's generated / cycled samples (contiguous rows of the passes' outputs) into the discriminators' batched inputs
+            after_fwd=None if prev is None else ([di["discriminator_B"][B:], di["discriminator_A"][B:]], [out[0][B2:], out[1][B2:]]),
+            after_cyc=None if prev is None else ([di["discriminator_A2"][B:], di["discriminator_B2"][B:]], [cyc2[0][B:], cyc2[1][B:]]))
+
+    def _g_parts(self, bd, fuse_update, laned=False, own_d_update=True, zero_mode=0, ranged=False, can_store=True):
+        """Parts of the generator phase (train.py:195-242) over the tensors of binding ``bd``.  ``laned``: emission (_emit); the laned
+        parts run each backward pass's weight gradients on their own lane's auxiliary stream and record each generator's own milestone
+        events, the grouped ones share lane 0's.  ``own_d_update`` (grouped): the first-step adversarial pair completes a deferred
+        discriminator update itself (plain step); the pipelined step orders the discriminators' update in front of the adversarial pairs
+        through the task graph instead.  ``zero_mode``: zero_grads mode of the update (0 / 1 / 2); ``can_store``: the cycle backward -- the
+        first weight-gradient pass over both generators -- may store into a store-ready buffer (``take``)."""
+        B, N = self.B, G_NAMES
+        sc = self.sched
+        cl, il = sc.cycle_loss_lambda, sc.identity_loss_lambda
+        g_lr = sc.g_opt_lr
+        g_cycle = (self.mel["g_cycle_A"], self.mel["g_cycle_B"])
+        do, dl, ds = self.dout1, self.dlogit1, self.d_stash1
         ov = self.overlap_g_reduce
         ms_on = ov or ranged                   # milestone events of the last backward pass: gradient exchange and / or ranged update
-        ident_dead = il == 0                   # (after the identity cut-off the identity passes are dead code: see generator_phase)
-        nbt = B if ident_dead else B2          # (the halves of the batched buffers are contiguous: translation first, identity second)
-        g_lr = sc.g_opt_lr
-        zero_mode = int(zeroing_update)
+        aux_lane, ms_of = (None, None) if laned else (0, N[0])
+        final = step_graphs.FINAL_LANED if laned else step_graphs.FINAL_GROUPED
         P = {}
         st = {"store": False}                  # the cycle backward stores (set by take(), before the tasks run)
 
-        copies = ([self.in_A2B[:B], self.in_A2B[B:], self.in_B2A[:B], self.in_B2A[B:], self.mask_A2B[:B], self.mask_B2A[:B]],
-                  [real_A, real_B, real_B, real_A, mask_A, mask_B])                    # (the masks' second halves stay all-ones)
+        def pair(name, f):
+            self._emit(P, laned, name, lambda k, slot: f(k))      # (a laned direction runs on lane k: its scratch and aux stream are k's)
+
         def take():
             st["store"] = self._take_grads("g", can_store)
 
@@ -631,66 +591,96 @@ class TrainEngine:
             self.slots[:_BLOCK].zero_()
             if zero_grads:
                 take()
-            torch._foreach_copy_(*copies)      # one launch
+            torch._foreach_copy_(*bd.copies)   # one launch
 
-        def fwd2(ln):                                                                                       # :203, :205, :207-210
-            self._twin(lambda: self._G(A2B, self.in_A2B, self.mask_A2B, self.out_A2B, self.g_stash2[0], nbt, 0),
-                       lambda: self._G(B2A, self.in_B2A, self.mask_B2A, self.out_B2A, self.g_stash2[1], nbt, 1))
+        def fwd(k):                                                                                         # :203, :205, :207-210
+            x, mask, out, stash = bd.fwd[k]
+            self._G(N[k], x, mask, out, stash, bd.nb_fwd, k)
 
-        def cycle_half(k):
-            if k == 0:
-                self._G(B2A, fake_B, None, m["cycle_A"], self.g_stash1[0], B, 0)                           # :204 (mask of ones)
-                self._l1(m["cycle_A"], real_A, cl, m["g_cycle_A"], 0)                                       # :219
-                if not ident_dead:
-                    self._l1(identity_B, real_B, il, g_identity_B, 3)                                       # :224
-            else:
-                self._G(A2B, fake_A, None, m["cycle_B"], self.g_stash1[1], B, 1)                           # :206
-                self._l1(m["cycle_B"], real_B, cl, m["g_cycle_B"], 1)                                       # :220
-                if not ident_dead:
-                    self._l1(identity_A, real_A, il, g_identity_A, 2)                                       # :223
+        def cyc_fwd(k):                                                                                     # :204, :206 (mask of ones)
+            self._G(N[1 - k], bd.cyc_in[k], None, bd.cyc_out[k], bd.cyc_stash[k], bd.nb_cyc, k)
 
-        def cycle(ln):
-            self._twin(lambda: cycle_half(0), lambda: cycle_half(1))
+        def cyc_l1(k):
+            self._l1(bd.cycle[k], bd.real[k], cl, g_cycle[k], k)                                            # :219, :220
+            if il != 0:
+                self._l1(bd.ident[k], bd.real[1 - k], il, bd.g_ident[k], 3 - k)                             # :224, :223
 
-        def adv_half(name, i, x, gx, acc):
+        if bd.merged:
+            def fwd_merged(ln):                                                                             # ... | :259, :267
+                if bd.repack:
+                    self._twin(lambda: self._repack1(N[0]), lambda: self._repack1(N[1]))
+                self._twin(lambda: fwd(0), lambda: fwd(1))
+                if bd.after_fwd is not None:
+                    torch._foreach_copy_(*bd.after_fwd)
+
+            def cycle_merged(ln):                                                                           # ... | :263, :271
+                self._twin(lambda: cyc_fwd(0), lambda: cyc_fwd(1))
+                if bd.after_cyc is not None:
+                    torch._foreach_copy_(*bd.after_cyc)
+                self._twin(lambda: cyc_l1(0), lambda: cyc_l1(1))
+            P["fwd"], P["cycle"] = fwd_merged, cycle_merged
+        else:
+            def cycle(k):
+                cyc_fwd(k)
+                cyc_l1(k)
+            pair("fwd", fwd)
+            pair("cycle", cycle)
+
+        def adv(i, x, gx, acc):
+            name = D_NAMES[i]
             self._D(name, x, do[i], ds[i], B, i)                                                            # :211-216
             self._lsgan(do[i], 1.0, 1.0, 4 + i, dl[i])                                                      # :227-231
             self._D_bwd(name, dl[i], gx, acc, ds[i], False, B, i)          # discriminators contribute data-gradients only
 
-        def adv1(ln):
-            if own_d_update:
-                self._finish_d_update()        # data parallel: the D all-reduce of the previous iteration hides behind the generator forwards
-            self._twin(lambda: adv_half("discriminator_A", 0, fake_A, g_fake_A, 0), lambda: adv_half("discriminator_B", 1, fake_B, g_fake_B, 0))
-            if own_d_update and fuse_update:
-                self._clear_grads("d")         # free once their Adam step is queued: cleared here, on the side lane (99 MB memset)
+        pair("adv1", lambda k: adv(k, bd.fake[1 - k], bd.g_fake[1 - k], 0))            # D_A(fake_A) | D_B(fake_B)
+        pair("adv2", lambda k: adv(2 + k, bd.cycle[k], g_cycle[k], 1))                 # D_A2(cycle_A) | D_B2(cycle_B)
 
-        def adv2(ln):
-            self._twin(lambda: adv_half("discriminator_A2", 2, m["cycle_A"], m["g_cycle_A"], 1),
-                       lambda: adv_half("discriminator_B2", 3, m["cycle_B"], m["g_cycle_B"], 1))
+        def finish_d(ln):
+            self._finish_d_update()            # data parallel: the D all-reduce of the previous iteration hides behind the generator forwards
+            if fuse_update:
+                # the discriminator gradients are free once their Adam step is queued: clear them here, on an idle lane, instead of
+                # on the caller's stream at the top of the discriminator phase (99 MB memset)
+                self._clear_grads("d")
+        if laned:
+            P["finish_d"] = finish_d
+        elif own_d_update:
+            adv1_pair = P["adv1"]
 
-        def bwd_cycle(ln):      # cycle_A = G_B2A(fake_B) adds to d(fake_B), cycle_B = G_A2B(fake_A) to d(fake_A)
-            self._twin(lambda: self._G_bwd(B2A, None, m["g_cycle_A"], g_fake_B, 1, self.g_stash1[0], B, 0, aux_lane=0, store=st["store"]),
-                       lambda: self._G_bwd(A2B, None, m["g_cycle_B"], g_fake_A, 1, self.g_stash1[1], B, 1, aux_lane=0, store=st["store"]))
+            def adv1(ln):
+                self._finish_d_update()
+                adv1_pair(ln)
+                if fuse_update:
+                    self._clear_grads("d")     # (as in finish_d, behind the pair on the side lane)
+            P["adv1"] = adv1
 
-        def bwd_final(ln):      # the last pass over each generator; its gradient ranges become final one after the other (milestone events)
-            self._twin(lambda: self._G_bwd(A2B, self.mask_A2B, self.gout_A2B, None, 0, self.g_stash2[0], nbt, 0, ms_on, aux_lane=0, ms_of=A2B),
-                       lambda: self._G_bwd(B2A, self.mask_B2A, self.gout_B2A, None, 0, self.g_stash2[1], nbt, 1, ms_on, aux_lane=0, ms_of=A2B))
+        def bwd_cycle(k):       # cycle_A = G_B2A(fake_B) adds to d(fake_B), cycle_B = G_A2B(fake_A) to d(fake_A)
+            self._G_bwd(N[1 - k], None, g_cycle[k], bd.g_fake[k], 1, bd.cyc_stash[k], B, k, aux_lane=aux_lane, no_join=bd.no_join,
+                        stash_nb=bd.nb_cyc, store=st["store"])
+
+        def bwd_final(k):       # the last pass over each generator; its gradient ranges become final one after the other (milestone events)
+            x, mask, out, stash = bd.fwd[k]
+            self._G_bwd(N[k], mask, bd.gout[k], None, 0, stash, bd.nb_bwd, bd.sc_final[k], ms_on, aux_lane=aux_lane, ms_of=ms_of, stash_nb=bd.nb_fwd)
+        pair("bwd_cycle", bwd_cycle)
+        pair("bwd_final", bwd_final)
 
         def queue_reduce(ln):
-            # data parallel: range k of BOTH generators is final at milestone k of the grouped pass; same collective order on every rank
-            for k in range(2):
-                for n in G_NAMES:
-                    lo, hi = self._g_ranges[n][k]
-                    self.reducer.reduce_range_after_(self.g_group.grad, lo, hi, self._ms[A2B][0][k])
-            for n in G_NAMES:
-                lo, hi = self._g_ranges[n][2]
-                self.reducer.reduce_range_after_(self.g_group.grad, lo, hi, self._task_events.get("f") if self.concurrent else None)
+            # data parallel: the generator gradients are exchanged range by range BEHIND the last backward passes (their milestone events;
+            # the tails behind the passes themselves), on the communication stream.  Serial mode records no task events (one stream:
+            # everything queued so far is the dependency); a stale event of an earlier concurrent iteration must not be used either
+            self._reduce_g_ranges(ms_of, [self._task_events.get(e) if self.concurrent else None for e in final])
+        P["queue_reduce"] = queue_reduce
 
         def update(ln):         # optimizer step of both generators + every packed copy, one grouped launch (train.py:242)
             self.reducer.wait(self.device)             # (no-op on one GPU)
             self._update_gens(g_lr, zero=zero_mode)
 
-        def update_range(k, last):
+        def update_half(k):     # ... of the generator whose last backward pass the lane ran: no join of the lanes, one launch per generator
+            if k == 0:
+                self.g_group.step += 1
+            self.reducer.wait(self.device)
+            self._update_gen(N[k], 7, g_lr, self.g_group.step, zero_mode)
+
+        def update_range(k):
             """Optimizer step (+ re-pack) of part k of both generators as grouped launches: 0 = up-sampling blocks + last conv, 1 = residual
             trunk, 2 = downSample2 + conv2dto1d, 3 = downSample1, 4 = conv1 -- the order in which a backward pass finishes them.  Parts 0-3
             wait for the pass's milestone events: their gradients are final while the pass is still running, so only conv1's (0.01 % of the
@@ -699,56 +689,44 @@ class TrainEngine:
 
             def run(ln):
                 if k < 4:
-                    torch.cuda.current_stream(self.device).wait_event(self._ms[A2B][0][k])
+                    torch.cuda.current_stream(self.device).wait_event(self._ms[N[0]][0][k])
                 if k == 0:
                     self.g_group.step += 1
                 step = self.g_group.step
-                self._twin(lambda: self._update_gen(A2B, mask, g_lr, step, zero_mode), lambda: self._update_gen(B2A, mask, g_lr, step, zero_mode))
+                self._twin(lambda: self._update_gen(N[0], mask, g_lr, step, zero_mode), lambda: self._update_gen(N[1], mask, g_lr, step, zero_mode))
             return run
 
         def post():
             self._g_fwd_packed = bool(fuse_update)
-            self._combine(0, self._comb_g)
-        P.update(update_range=update_range, pre=pre, take=take, zero_mode=zero_mode, fwd2=fwd2, cycle=cycle, adv1=adv1, adv2=adv2, bwd_cycle=bwd_cycle, bwd_final=bwd_final,
-                 queue_reduce=queue_reduce, update=update, post=post, ov=ov, copies=copies)
-        return P
+            self._combine(0, self._comb_g)          # g_loss and its terms, summed in the reference's order (:233-237)
+        if laned:
+            pair("update", update_half)
+        else:
+            P["update"] = update
+            P["g_post"] = lambda ln: post()
+            for k in range(5):
+                P["update_range%d" % k] = update_range(k)
+        assert P.keys() == step_graphs.G_PARTS[laned], sorted(P.keys() ^ step_graphs.G_PARTS[laned])
+        return SimpleNamespace(parts=P, pre=pre, take=take, post=post, copies=bd.copies)
 
-    def generator_phase_grouped(self, real_A, mask_A, real_B, mask_B, fuse_update=False):
-        """train.py:195-242 with the two generators (and each discriminator pair) in grouped launches: the same dataflow as
-        ``generator_phase`` on two lanes.  Lane 0: both translation (+ identity) passes, both cycle passes, the second-step discriminators,
-        both backward rounds, the update.  Lane 1: the first-step adversarial pair D_A(fake_A) | D_B(fake_B), which needs only the
-        translated batches and runs beside the cycle forwards."""
-        p = self._g_parts((real_A, mask_A, real_B, mask_B), fuse_update, zeroing_update=self._zero_mode() if fuse_update else 0)
-        p["pre"]()
-        ov = p["ov"]
-        self._run_tasks([
-            (0, p["fwd2"], (), "g"),
-            (0, p["cycle"], (), None),
-            (1, p["adv1"], ("g",), "d1"),
-            (0, p["adv2"], (), None),
-            (0, p["bwd_cycle"], ("d1",), None),
-            (0, p["bwd_final"], (), "f"),
-        ] + ([(1, p["queue_reduce"], (), None)] if (fuse_update and ov) else [])
-          + ([(0, p["update"], (), None)] if fuse_update else []))
-        if fuse_update:
-            self._grads_updated("g", p["zero_mode"])          # (cleared, or left store-ready, by the update launch that consumed them)
-        p["post"]()
-
-    def _d_parts(self, inp, gi=0, aux2=None, can_store=True):
-        """Closures of the discriminator phase (train.py:247-299) in grouped launches.  ``gi``: index of the (stash, scratch) pair its two
-        generator forwards use -- 0 = the cycle passes' (plain step: the phases run one after the other), 2 = their own (pipelined step:
-        they run beside the next iteration's generator phase).  ``can_store``: each discriminator's first weight-gradient pass (full, or
-        the real half of a split phase) may store into a store-ready buffer (``take``)."""
+    def _d_parts(self, inp, laned=False, gi=0, aux2=None, can_store=True, update=(None, None, 1)):
+        """Parts of the discriminator phase (train.py:247-299).  ``gi``: index of the (stash, scratch) pair its two generator forwards use
+        -- 0 = the cycle passes' (plain step: the phases run one after the other), 2 = their own (pipelined step: they run beside the next
+        iteration's generator phase).  ``aux2``: stream for the second-step pair's weight gradients.  ``can_store``: each discriminator's
+        first weight-gradient pass (full, or the real half of a split phase) may store into a store-ready buffer (``take``).  ``update``:
+        (lr, Adam step, zero_grads mode) of the per-pair updates ``dupd1`` / ``dupd2``."""
         real_A, mask_A, real_B, mask_B = inp
-        B, B2 = self.B, 2 * self.B
+        B, B2, N = self.B, 2 * self.B, G_NAMES
         di = self.d_in
-        gen_A, gen_B = di["discriminator_A"][B:], di["discriminator_B"][B:]
-        cyc_A, cyc_B = di["discriminator_A2"][B:], di["discriminator_B2"][B:]
+        # generators run with their UPDATED weights and no gradient (train.py:259-273); outputs land directly in the second half of the
+        # discriminators' batched inputs
+        real, mask = (real_A, real_B), (mask_A, mask_B)
+        gen = (di["discriminator_B"][B:], di["discriminator_A"][B:])                   # generated_B, generated_A
+        cyc = (di["discriminator_A2"][B:], di["discriminator_B2"][B:])                 # cycled_A, cycled_B
         do, dl, ds = self.dout2, self.dlogit2, self.d_stash2
-        idx = {n: i for i, n in enumerate(D_NAMES)}
-        A2B, B2A = G_NAMES
         gst = self.g_stash1 if gi == 0 else self.g_stashD
-        s0, s1 = (0, 1) if gi == 0 else (4, 5)
+        sidx = (0, 1) if gi == 0 else (4, 5)
+        packed = self._g_fwd_packed
         P = {}
         st = {"store": False}
 
@@ -762,81 +740,96 @@ class TrainEngine:
                 take()
             torch._foreach_copy_(*copies)
 
-        def disc_full(name):
-            i = idx[name]
+        def disc_full(i, slot):
+            name = D_NAMES[i]
             self._D(name, di[name], do[i], ds[i], B2, i)                       # :255-258 real half, :260-273 generated half
-            self._lsgan(do[i][:B], 1.0, 0.25, 8 + 2 * i, dl[i][:B])            # every term of d_loss weighs 1/4 (:276-294)
+            # d_loss = (A + B)/2 + (A_2nd + B_2nd)/2 with each = (real + fake)/2  -> every term weighs 1/4  (:276-294)
+            self._lsgan(do[i][:B], 1.0, 0.25, 8 + 2 * i, dl[i][:B])
             self._lsgan(do[i][B:], 0.0, 0.25, 9 + 2 * i, dl[i][B:])
             # (pipelined step: the second-step pair closes the critical chain; its weight gradients run on an idle lane's stream)
-            self._D_bwd(name, dl[i], None, 0, ds[i], True, B2, i, aux_stream=aux2 if i >= 2 else None, store=st["store"])
+            self._D_bwd(name, dl[i], None, 0, ds[i], True, B2, i, aux_stream=aux2 if i >= 2 else None, aux_lane=slot if laned else None,
+                        store=st["store"])
 
-        def disc_half(name, fake):
-            i = idx[name]
+        def disc_half(i, slot, fake):
+            name = D_NAMES[i]
             sl = slice(B, B2) if fake else slice(0, B)
             stash = ds[i] if fake else self.d_stash1[i]
             self._D(name, di[name][sl], do[i][sl], stash, B, i)
             self._lsgan(do[i][sl], 0.0 if fake else 1.0, 0.25, 8 + 2 * i + int(fake), dl[i][sl])
-            self._D_bwd(name, dl[i][sl], None, 0, stash, True, B, i, store=st["store"] and not fake)      # (the real half runs first)
+            self._D_bwd(name, dl[i][sl], None, 0, stash, True, B, i, aux_lane=slot if laned else None,
+                        store=st["store"] and not fake)                                                      # (the real half runs first)
 
-        def pair(fn, a, b, *args):
-            return lambda ln: self._twin(lambda: fn(a, *args), lambda: fn(b, *args))
-
-        def gen_fwd(ln):
-            self._twin(lambda: self._G(A2B, real_A, mask_A, gen_B, gst[0], B, s0),                          # :267 generated_B
-                       lambda: self._G(B2A, real_B, mask_B, gen_A, gst[1], B, s1))                          # :259 generated_A
-
-        def cycles(ln):
-            self._twin(lambda: self._G(B2A, gen_B, None, cyc_A, gst[0], B, s0),                             # :271 cycled_A
-                       lambda: self._G(A2B, gen_A, None, cyc_B, gst[1], B, s1))                             # :263 cycled_B
-
-        def repack_full(ln):
-            self._twin(lambda: self._repack1(A2B), lambda: self._repack1(B2A))
-
-        def post():
-            self._combine(8, self._comb_d)
-        P.update(pre=pre, take=take, gen_fwd=gen_fwd, cycles=cycles, repack_full=repack_full, post=post, copies=copies,
-                 full1=pair(disc_full, "discriminator_A", "discriminator_B"), full2=pair(disc_full, "discriminator_A2", "discriminator_B2"),
-                 real1=pair(disc_half, "discriminator_A", "discriminator_B", False), real2=pair(disc_half, "discriminator_A2", "discriminator_B2", False),
-                 fake1=pair(disc_half, "discriminator_A", "discriminator_B", True), fake2=pair(disc_half, "discriminator_A2", "discriminator_B2", True))
-        return P
-
-    def discriminator_phase_grouped(self, real_A, mask_A, real_B, mask_B):
-        """train.py:247-299, grouped like ``generator_phase_grouped``: lane 0 runs both generators' forwards (translation, then cycle) and
-        the second-step discriminator pair, lane 1 runs D_A | D_B."""
-        p = self._d_parts((real_A, mask_A, real_B, mask_B))
-        p["pre"]()
-        packed = self._g_fwd_packed
-        self._g_fwd_packed = False
-
-        def gen_fwd(ln):
-            if not packed:                     # phase called on its own (the caller may have written parameters): full refresh first
-                p["repack_full"](ln)
-            p["gen_fwd"](ln)
+        # (a generator pass works in the stash and scratch of its slot: laned, the lane it runs on; grouped, its direction)
+        self._emit(P, laned, "gen_fwd", lambda k, s: self._G(N[k], real[k], mask[k], gen[k], gst[s], B, sidx[s]))        # :267, :259
+        self._emit(P, laned, "d_cycles", lambda k, s: self._G(N[1 - k], gen[k], None, cyc[k], gst[s], B, sidx[s]))       # :271, :263
+        self._emit(P, laned, "repack", lambda k, s: self._repack1(N[k]))
+        for j in (0, 1):                       # the first- and the second-step pair: D_A | D_B, D_A2 | D_B2
+            self._emit(P, laned, "full%d" % (j + 1), lambda k, s, j=j: disc_full(2 * j + k, s))
+            self._emit(P, laned, "real%d" % (j + 1), lambda k, s, j=j: disc_half(2 * j + k, s, False))
+            self._emit(P, laned, "fake%d" % (j + 1), lambda k, s, j=j: disc_half(2 * j + k, s, True))
 
         def refresh(ln):                       # beside the generator forwards; the generator gradients are free by now
             if packed:
-                self._clear_grads("g")         # (196 MB memset on the side lane instead of at the top of the next iteration)
-        if self.B >= self.split_d_min_batch:
-            # the real halves need nothing from the generators: lane 1 runs them while lane 0 is in the generator forwards
-            tasks = [
-                (0, gen_fwd, (), "gen"),
-                (1, refresh, (), None),
-                (1, p["real1"], (), None),
-                (1, p["real2"], (), "r2"),
-                (0, p["cycles"], (), None),
-                (1, p["fake1"], ("gen",), None),
-                (0, p["fake2"], ("r2",), None),
-            ]
-        else:
-            tasks = [
-                (0, gen_fwd, (), "gen"),
-                (1, refresh, (), None),
-                (0, p["cycles"], (), None),
-                (1, p["full1"], ("gen",), None),
-                (0, p["full2"], (), None),
-            ]
-        self._run_tasks(tasks)
-        p["post"]()
+                self._clear_grads("g")         # (196 MB memset on an idle lane instead of at the top of the next iteration)
+        P["refresh"] = refresh
+
+        def post():
+            self._combine(8, self._comb_d)
+        if not laned:
+            gen_fwd_pair = P["gen_fwd"]
+
+            def gen_fwd(ln):
+                if not packed:                 # phase called on its own (the caller may have written parameters): full refresh first
+                    P["repack"](ln)
+                gen_fwd_pair(ln)
+
+            def post_publish(ln):              # d_loss and its terms of iteration t: the iteration is complete
+                post()
+                self.slots_done[_BLOCK:].copy_(self.slots[_BLOCK:])
+                self._publish_done()
+            P.update(gen_fwd=gen_fwd, d_post_publish=post_publish,
+                     dupd1=self._d_pair_update(D_NAMES[:2], *update), dupd2=self._d_pair_update(D_NAMES[2:], *update))
+        assert P.keys() == step_graphs.D_PARTS[laned], sorted(P.keys() ^ step_graphs.D_PARTS[laned])
+        return SimpleNamespace(parts=P, pre=pre, take=take, post=post, copies=copies)
+
+    def _g_phase(self, inp, fuse_update, laned):
+        # (four lanes: no store mode; the update leaves the gradients dirty, an idle lane of the discriminator phase clears them)
+        zm = self._zero_mode() if (fuse_update and not laned) else 0
+        g = self._g_parts(self._bind_plain(inp), fuse_update, laned=laned, zero_mode=zm, can_store=not laned)
+        g.pre()
+        graph = step_graphs.four_lane_g if laned else step_graphs.grouped_g
+        self._run_tasks(graph(fuse_update, self.overlap_g_reduce), g.parts)
+        if fuse_update:
+            self._grads_updated("g", zm)       # (cleared, or left store-ready, by the update launch that consumed them)
+        g.post()
+
+    def _d_phase(self, inp, laned):
+        d = self._d_parts(inp, laned=laned, can_store=not laned)
+        d.pre()
+        packed = self._g_fwd_packed
+        self._g_fwd_packed = False
+        split = self.B >= self.split_d_min_batch
+        self._run_tasks(step_graphs.four_lane_d(packed, split) if laned else step_graphs.grouped_d(split), d.parts)
+        d.post()
+
+    def generator_phase(self, real_A, mask_A, real_B, mask_B, fuse_update=False):
+        """train.py:195-242 on four lanes (more than ``grouped_max_b`` samples per pass; step_graphs.four_lane_g).  ``fuse_update`` (what
+        ``step()`` uses): each lane also runs the optimizer step of the generator whose last backward pass it ran, fused with the refresh
+        of its packed copies (train.py:242) -- no join of the lanes, one launch per generator."""
+        self._g_phase((real_A, mask_A, real_B, mask_B), fuse_update, True)
+
+    def generator_phase_grouped(self, real_A, mask_A, real_B, mask_B, fuse_update=False):
+        """train.py:195-242 with the two generators (and each discriminator pair) in grouped launches: the same parts on two lanes
+        (step_graphs.grouped_g)."""
+        self._g_phase((real_A, mask_A, real_B, mask_B), fuse_update, False)
+
+    def discriminator_phase(self, real_A, mask_A, real_B, mask_B):
+        """train.py:247-299 on four lanes (step_graphs.four_lane_d)."""
+        self._d_phase((real_A, mask_A, real_B, mask_B), True)
+
+    def discriminator_phase_grouped(self, real_A, mask_A, real_B, mask_B):
+        """train.py:247-299, grouped like ``generator_phase_grouped`` (step_graphs.grouped_d)."""
+        self._d_phase((real_A, mask_A, real_B, mask_B), False)
 
     def _d_pair_update(self, pair, d_lr, d_step, zero_mode=1):
         """Task: optimizer step of one discriminator pair (its slice of the flat buffer; data parallel: behind its all-reduce) fused with the
@@ -857,12 +850,7 @@ class TrainEngine:
         The discriminator phase of an iteration (train.py:247-299) reads the generators as updated by that iteration's generator phase
         and writes the discriminators; the NEXT iteration's generator forwards (translation, identity, cycle: train.py:203-210) read the
         same generator weights and no discriminator at all -- only its adversarial passes (:211-216) need the updated discriminators,
-        and each pair only its own two networks.  So a step issues, as ONE task graph:
-            lane 1:  D-phase(t): generator forwards -> cycle forwards -> D_A2 | D_B2 -> [all-reduce] update of their slice -> "dupd2";
-                     then the ranged generator update of G-phase(t+1) behind the last backward pass's milestone events
-            lane 3:  D_A | D_B of D-phase(t) -> update of their slice -> "dupd1"; the backward rounds' weight gradients
-            lane 0:  G-phase(t+1): translation (+ identity) -> cycle -> (dupd2) D_A2 | D_B2 adversarial -> backward x 2 -> conv1's update
-            lane 2:  (dupd1) the first-step adversarial pair of G-phase(t+1)
+        and each pair only its own two networks.  So a step issues both as ONE task graph (step_graphs.pipelined has the lane map).
         Every quantity is computed from exactly the weights and inputs the reference uses (the order of the optimizers' steps is kept:
         a discriminator's Adam step (t) is complete before it is read by iteration t+1; Adam(G)(t+1) waits for D-phase(t)'s generator
         forwards); two generator-forward latencies leave the critical path of every iteration.  The update launches clear the gradients
@@ -872,61 +860,29 @@ class TrainEngine:
         prev, d_lr = self._pending_D if self._pending_D is not None else (None, None)
         ranged = not self.reducer.active
         zm = self._zero_mode()
-        g = self._g_parts(cur, True, own_d_update=prev is None, zeroing_update=zm, ranged=ranged)
-        ov = g["ov"]
+        ov = self.overlap_g_reduce
+        g = self._g_parts(self._bind_plain(cur), True, own_d_update=prev is None, zero_mode=zm, ranged=ranged)
         if prev is None:                       # first iteration (or the first after a flush): there is no discriminator phase to run beside it
-            g["pre"](zero_grads=True)
-            tasks = [(0, g["fwd2"], (), "g"), (0, g["cycle"], (), None), (2, g["adv1"], ("g",), "d1"), (0, g["adv2"], (), None),
-                     (0, g["bwd_cycle"], ("d1",), None), (0, g["bwd_final"], (), "f")]
-            tasks += ([(3, g["queue_reduce"], (), None)] if ov else []) + [(0, g["update"], (), None)]
-            self._run_tasks(tasks)
+            g.pre()
+            self._run_tasks(step_graphs.grouped_g(True, ov, lanes=(2, 3)), g.parts)
             self._grads_updated("g", zm)       # (cleared, or left store-ready, by the update launch that consumed them)
-            g["post"]()
+            g.post()
             return
-        d = self._d_parts(prev, gi=2, aux2=self._sides[1])            # (lane 2's stream: idle until "dupd1")
-        g["take"](), d["take"]()               # (no memset: the updates that consumed the gradients cleared them or left them store-ready)
+        d_step = self.d_group.step + 1
+        d = self._d_parts(prev, gi=2, aux2=self._sides[1], update=(d_lr, d_step, zm))            # (lane 2's stream: idle until "dupd1")
+        g.take(), d.take()                     # (no memset: the updates that consumed the gradients cleared them or left them store-ready)
         # caller's stream, before the lanes fork, TWO launches (five until r5, ~15 us of idle GPU each at the head of the chain): iteration t's g_loss
         # terms saved + both phases' input copies; both loss blocks cleared (the gradients were cleared by the updates that consumed them)
-        torch._foreach_copy_([self.slots_done[:_BLOCK]] + g["copies"][0] + d["copies"][0], [self.slots[:_BLOCK]] + g["copies"][1] + d["copies"][1])
+        torch._foreach_copy_([self.slots_done[:_BLOCK]] + g.copies[0] + d.copies[0], [self.slots[:_BLOCK]] + g.copies[1] + d.copies[1])
         self.slots.zero_()
-        packed = self._g_fwd_packed
-        d_step = self.d_group.step + 1
         split, tail = self.B >= self.split_d_min_batch, self.concurrent and not self._serial
         serial = self._serial_fwd()            # (data-parallel ranks: one grouped persistent trunk pass in flight at a time)
-        tasks = [
-            (1, (lambda ln: (None if packed else d["repack_full"](ln), d["gen_fwd"](ln))), (), "gen"),
-        ] + ([(1, d["cycles"], (), "cyc")] if serial else []) + [
-            (0, g["fwd2"], ("cyc",) if serial else (), "g"),
-        ]
-        if split:
-            tasks += [(3, d["real1"], (), None), (3, d["real2"], (), "r2")]
-        tasks += ([] if serial else [(1, d["cycles"], (), "cyc")]) + [
-            (0, g["cycle"], (), None),
-            (3, d["fake1"] if split else d["full1"], ("gen",), None),
-            (3, self._d_pair_update(("discriminator_A", "discriminator_B"), d_lr, d_step, zm), (), "dupd1"),
-            (1, d["fake2"] if split else d["full2"], ("r2",) if split else (), None),
-            (1, self._d_pair_update(("discriminator_A2", "discriminator_B2"), d_lr, d_step, zm), (), "dupd2"),
-            (2, g["adv1"], ("g", "dupd1"), "d1"),
-        ] + ([(2, lambda ln: (d["post"](), self.slots_done[_BLOCK:].copy_(self.slots[_BLOCK:]), self._publish_done()), ("dupd2",), None)] if tail else []) + [
-            (0, g["adv2"], ("dupd2",), None),
-            (0, g["bwd_cycle"], ("d1",), None),
-            (0, g["bwd_final"], (), "f"),
-        ] + ([(2, lambda ln: g["post"](), ("f",), None)] if tail else []) + ([(3, g["queue_reduce"], (), None)] if ov else [])
-        if ranged:
-            # the generator update range by range: the up-sampling blocks', the trunk's and most of the head's optimizer step + re-pack run
-            # on lane 1 (idle since "dupd2" -- lane 3's stream carries the backward rounds' weight gradients) beside the rest of the last
-            # backward pass, behind its milestone events and after everything that still reads the old weights (D-phase(t)'s generator
-            # forwards: "cyc"); only conv1's is left for the end of the chain
-            tasks += [(1, g["update_range"](0, False), ("cyc",), None), (1, g["update_range"](1, False), (), None),
-                      (1, g["update_range"](2, False), (), None), (1, g["update_range"](3, False), (), None),
-                      (0, g["update_range"](4, True), ("cyc",), None)]
-        else:
-            tasks += [(0, g["update"], ("cyc",), None)]
-        self._run_tasks(tasks)
+        self._run_tasks(step_graphs.pipelined(split, serial, ranged, ov, tail), {**g.parts, **d.parts})
         self.d_group.step = d_step
         self._grads_updated("g", zm), self._grads_updated("d", zm)
         if not tail:      # (tail: the loss sums and the publish of iteration t's losses ride on lanes 1 / 2 instead of the end of the chain)
-            g["post"](), d["post"](), self.slots_done[_BLOCK:].copy_(self.slots[_BLOCK:]), self._publish_done()
+            g.post()
+            d.parts["d_post_publish"](0)
 
     # ---- merged forwards (r4) ---------------------------------------------------------------------------------------------------------
     def _merged_ok(self, B):
@@ -954,108 +910,26 @@ class TrainEngine:
             [ identity: real_other(t+1) | ones ;  translation: real(t+1) | mask(t+1) ;  D-phase translation: real(t) | mask(t) ]
         and the cycle pass TWO: [ fake(t+1) ; generated(t) ] (contiguous rows of the first pass's output).  The backward passes run over the
         first two / the first sample of those stashes (mcvc_gen_backward_window).  Per-sample results are what the separate passes compute
-        (every op of the generator is per sample): tests/test_hip_twin.py.  Two of six grouped generator passes disappear; one persistent trunk pass in flight, not two.
-            lane 0: forward x3 -> cycle x2 -> the two backward passes -> conv1's update;  lanes 1 / 2: D_A | D_B (D_A2 | D_B2) of D-phase(t) ->
-            their update -> first- (second-) step adversarial pair of G-phase(t+1), lane 1 then the ranged generator update;  lane 3: weight gradients"""
-        cur = self.static_in
+        (every op of the generator is per sample): tests/test_hip_twin.py.  Two of six grouped generator passes disappear; one persistent
+        trunk pass in flight, not two.  The same parts as the other schedules over the merged binding (_bind_merged), no store mode;
+        step_graphs.merged has the lane map."""
         prev, d_lr = self._pending_D if self._pending_D is not None else (None, None)
-        B, B2, B3 = self.B, 2 * self.B, 3 * self.B
-        A2B, B2A = G_NAMES
-        sc = self.sched
-        cl, il = sc.cycle_loss_lambda, sc.identity_loss_lambda
         ranged = not self.reducer.active
-        g = self._g_parts(cur, True, own_d_update=False, zeroing_update=1, ranged=ranged, can_store=False)     # (update / reduce / post closures; no store mode)
-        ov = g["ov"]
-        ms_on = ov or ranged
-        real_A, mask_A, real_B, mask_B = cur
-        p_real_A, p_mask_A, p_real_B, p_mask_B = prev if prev is not None else cur          # (first iteration: a throw-away third sample)
-        in3, mask3, out3, gout3, cyc2 = self.in3, self.mask3, self.out3, self.gout3, self.cyc2
-        identity_B, fake_B, gen_B = out3[A2B][:B], out3[A2B][B:B2], out3[A2B][B2:]
-        identity_A, fake_A, gen_A = out3[B2A][:B], out3[B2A][B:B2], out3[B2A][B2:]
-        g_identity_B, g_fake_B = gout3[A2B][:B], gout3[A2B][B:]
-        g_identity_A, g_fake_A = gout3[B2A][:B], gout3[B2A][B:]
-        cycle_A, cyc_A = cyc2["A"][:B], cyc2["A"][B:]
-        cycle_B, cyc_B = cyc2["B"][:B], cyc2["B"][B:]
-        m = self.mel
-        di = self.d_in
-        do, dl, ds = self.dout1, self.dlogit1, self.d_stash1
-        d = self._d_parts(prev, gi=2, aux2=None, can_store=False) if prev is not None else None
-        if prev is not None:
-            self.slots_done[:_BLOCK].copy_(self.slots[:_BLOCK])       # g_loss and its terms of iteration t, before the block is reused
-        # ---- on the caller's stream, before the lanes fork
-        self.slots[:_BLOCK].zero_()
-        self._take_grads("g")
-        torch._foreach_copy_(
-            [in3[A2B][:B], in3[A2B][B:B2], in3[A2B][B2:], mask3[A2B][B:B2], mask3[A2B][B2:],
-             in3[B2A][:B], in3[B2A][B:B2], in3[B2A][B2:], mask3[B2A][B:B2], mask3[B2A][B2:]],
-            [real_B, real_A, p_real_A, mask_A, p_mask_A,
-             real_A, real_B, p_real_B, mask_B, p_mask_B])                # (the identity samples' masks stay all-ones)
-        if d is not None:
-            d["pre"](zero_grads=not self._d_grad_clean)
-        packed = self._g_fwd_packed
         d_step = self.d_group.step + 1
-
-        def fwd3(ln):                                                                                       # :203, :205, :207-210 | :259, :267
-            if not packed:
-                self._twin(lambda: self._repack1(A2B), lambda: self._repack1(B2A))
-            self._twin(lambda: self._G(A2B, in3[A2B], mask3[A2B], out3[A2B], self.g_stash3x[0], B3, 0),
-                       lambda: self._G(B2A, in3[B2A], mask3[B2A], out3[B2A], self.g_stash3x[1], B3, 1))
-            if d is not None:
-                torch._foreach_copy_([di["discriminator_B"][B:], di["discriminator_A"][B:]], [gen_B, gen_A])
-
-        def cycle2(ln):                                                                                     # :204, :206 | :263, :271
-            self._twin(lambda: self._G(B2A, out3[A2B][B:], None, cyc2["A"], self.g_stash2c[0], B2, 0),
-                       lambda: self._G(A2B, out3[B2A][B:], None, cyc2["B"], self.g_stash2c[1], B2, 1))
-            if d is not None:
-                torch._foreach_copy_([di["discriminator_A2"][B:], di["discriminator_B2"][B:]], [cyc_A, cyc_B])
-            self._twin(lambda: (self._l1(cycle_A, real_A, cl, m["g_cycle_A"], 0), self._l1(identity_B, real_B, il, g_identity_B, 3)),   # :219, :224
-                       lambda: (self._l1(cycle_B, real_B, cl, m["g_cycle_B"], 1), self._l1(identity_A, real_A, il, g_identity_A, 2)))   # :220, :223
-
-        def adv_half(name, i, x, gx, acc):
-            self._D(name, x, do[i], ds[i], B, i)                                                            # :211-216
-            self._lsgan(do[i], 1.0, 1.0, 4 + i, dl[i])                                                      # :227-231
-            self._D_bwd(name, dl[i], gx, acc, ds[i], False, B, i)          # discriminators contribute data-gradients only
-
-        def adv1(ln):
-            self._twin(lambda: adv_half("discriminator_A", 0, fake_A, g_fake_A, 0), lambda: adv_half("discriminator_B", 1, fake_B, g_fake_B, 0))
-
-        def adv2(ln):
-            self._twin(lambda: adv_half("discriminator_A2", 2, cycle_A, m["g_cycle_A"], 1),
-                       lambda: adv_half("discriminator_B2", 3, cycle_B, m["g_cycle_B"], 1))
-
-        # The cycle pass's weight gradients (auxiliary stream) outlast its data-gradient chain by ~0.2 ms; the translation pass needs only the
-        # data gradient, so it starts without that join (MCVC_BWD_NO_JOIN, include/mcvc.h): its own weight gradients queue behind them on the
-        # same auxiliary stream (same tensors, in order), it works in other scratch buffers (4, 5), and its final join covers both passes.
-        def bwd_cycle(ln):      # cycle_A = G_B2A(fake_B) adds to d(fake_B), cycle_B = G_A2B(fake_A) to d(fake_A)
-            self._twin(lambda: self._G_bwd(B2A, None, m["g_cycle_A"], g_fake_B, 1, self.g_stash2c[0], B, 0, aux_lane=0, no_join=True, stash_nb=B2),
-                       lambda: self._G_bwd(A2B, None, m["g_cycle_B"], g_fake_A, 1, self.g_stash2c[1], B, 1, aux_lane=0, no_join=True, stash_nb=B2))
-
-        def bwd_final(ln):      # identity + translation samples; the gradient ranges become final one after the other (milestone events)
-            self._twin(lambda: self._G_bwd(A2B, mask3[A2B], gout3[A2B], None, 0, self.g_stash3x[0], B2, 4, ms_on, aux_lane=0, ms_of=A2B, stash_nb=B3),
-                       lambda: self._G_bwd(B2A, mask3[B2A], gout3[B2A], None, 0, self.g_stash3x[1], B2, 5, ms_on, aux_lane=0, ms_of=A2B, stash_nb=B3))
-
-        tasks = [(0, fwd3, (), "g"), (0, cycle2, (), "c")]
+        g = self._g_parts(self._bind_merged(self.static_in, prev), True, own_d_update=False, zero_mode=1, ranged=ranged, can_store=False)
+        d = self._d_parts(prev, gi=2, can_store=False, update=(d_lr, d_step, 1)) if prev is not None else None
         if d is not None:
-            tasks += [(1, d["full1"], ("g",), None), (1, self._d_pair_update(("discriminator_A", "discriminator_B"), d_lr, d_step), (), None),
-                      (2, d["full2"], ("c",), None), (2, self._d_pair_update(("discriminator_A2", "discriminator_B2"), d_lr, d_step), (), None)]
-        tasks += [(1, adv1, ("g",), "d1"), (2, adv2, ("c",), "d2"),
-                  (0, bwd_cycle, ("d1", "d2"), None), (0, bwd_final, (), "f")]
-        if ov:
-            tasks += [(3, g["queue_reduce"], (), None)]
-        if ranged:
-            tasks += [(1, g["update_range"](0, False), (), None), (1, g["update_range"](1, False), (), None),
-                      (1, g["update_range"](2, False), (), None), (1, g["update_range"](3, False), (), None), (0, g["update_range"](4, True), (), None)]
-        else:
-            tasks += [(0, g["update"], (), None)]
-        self._run_tasks(tasks)
+            self.slots_done[:_BLOCK].copy_(self.slots[:_BLOCK])       # g_loss and its terms of iteration t, before the block is reused
+        g.pre()                                # on the caller's stream, before the lanes fork
+        if d is not None:
+            d.pre(zero_grads=not self._d_grad_clean)
+        self._run_tasks(step_graphs.merged(d is not None, ranged, self.overlap_g_reduce), {**g.parts, **(d.parts if d is not None else {})})
         self._grads_updated("g", 1)            # (cleared by the update launches that consumed them)
-        g["post"]()
+        g.post()
         if d is not None:
             self.d_group.step = d_step
             self._grads_updated("d", 1)
-            d["post"]()
-            self.slots_done[_BLOCK:].copy_(self.slots[_BLOCK:])           # d_loss and its terms of iteration t: the iteration is complete
-            self._publish_done()
+            d.parts["d_post_publish"](0)
 
     def _publish_done(self):
         """Losses of the last COMPLETE iteration to pinned host memory (asynchronous copy + event; ``losses(lagged=True)`` waits for it)."""
@@ -1064,114 +938,27 @@ class TrainEngine:
         ev.record()
         self._done_count += 1
 
+    def _reduce_g_ranges(self, ms_of, final):
+        """Queue the all-reduce of the generator gradient ranges in THE collective order, the same on every rank: range k of A2B, range k
+        of B2A, k = 0, 1, each behind milestone event k of the last backward pass (of generator ``ms_of``: range k of BOTH generators is
+        final at milestone k of a grouped pass; None: each generator's own), then the two tails behind the events ``final`` (None:
+        behind everything queued so far)."""
+        for k in range(2):
+            for n in G_NAMES:
+                lo, hi = self._g_ranges[n][k]
+                self.reducer.reduce_range_after_(self.g_group.grad, lo, hi, self._ms[ms_of or n][0][k])
+        for n, ev in zip(G_NAMES, final):
+            lo, hi = self._g_ranges[n][2]
+            self.reducer.reduce_range_after_(self.g_group.grad, lo, hi, ev)
+
     def generator_update(self):
         """All-reduce (data parallel) + optimizer step of both generators (train.py:242) behind a generator phase that ran without its own."""
         if self.overlap_g_reduce:
-            # same collective order on every rank: range k of A2B, range k of B2A, k = 0, 1, then the two tails
-            for k in range(2):
-                for n in G_NAMES:
-                    lo, hi = self._g_ranges[n][k]
-                    self.reducer.reduce_range_after_(self.g_group.grad, lo, hi, self._ms[n][0][k])
-            for n in G_NAMES:
-                lo, hi = self._g_ranges[n][2]
-                self.reducer.reduce_range_after_(self.g_group.grad, lo, hi, None)
+            self._reduce_g_ranges(None, (None, None))
             self.reducer.wait(self.device)
         else:
             self.reducer.reduce_(self.g_group.grad)
         self._update_gens(self.sched.g_opt_lr)
-
-    def discriminator_phase(self, real_A, mask_A, real_B, mask_B):
-        """train.py:247-299 on four lanes."""
-        B, B2 = self.B, 2 * self.B
-        self.slots[_BLOCK:].zero_()
-        self._take_grads("d")
-        di = self.d_in
-        # generators run with their UPDATED weights and no gradient (train.py:259-273); outputs land directly in the
-        # second half of the discriminators' batched inputs
-        gen_A, gen_B = di["discriminator_A"][B:], di["discriminator_B"][B:]
-        cyc_A, cyc_B = di["discriminator_A2"][B:], di["discriminator_B2"][B:]
-        torch._foreach_copy_([di["discriminator_A"][:B], di["discriminator_A2"][:B], di["discriminator_B"][:B], di["discriminator_B2"][:B]],
-                             [real_A, real_A, real_B, real_B])
-        do, dl, ds = self.dout2, self.dlogit2, self.d_stash2
-        idx = {n: i for i, n in enumerate(D_NAMES)}
-
-        def disc(name):
-            i = idx[name]
-
-            def run(ln):
-                self._D(name, di[name], do[i], ds[i], B2, ln)                      # :255-258 real half, :260-273 generated half
-                # d_loss = (A + B)/2 + (A_2nd + B_2nd)/2 with each = (real + fake)/2  -> every term weighs 1/4  (:276-294)
-                self._lsgan(do[i][:B], 1.0, 0.25, 8 + 2 * i, dl[i][:B])
-                self._lsgan(do[i][B:], 0.0, 0.25, 9 + 2 * i, dl[i][B:])
-                self._D_bwd(name, dl[i], None, 0, ds[i], True, B2, ln)
-            return run
-        # Same shape as the generator phase: lanes 0/1 carry the two generator chains, D_A / D_B need only the generated batches and run
-        # on lanes 2/3 while lanes 0/1 are in the cycle forwards; the second-step discriminators follow the cycle forwards on lanes 0/1.
-        if self._g_fwd_packed:
-            # the generator phase left lane 0 with generator_A2B updated and its copies fresh, lane 1 with generator_B2A: each lane starts
-            # with its own generator
-            self._g_fwd_packed = False
-
-            def clear_g(ln):
-                self.g_group.grad.zero_()      # the generator gradients are free (their update ended the generator phase): 196 MB
-                self._grads_updated("g", 1)    # memset on an idle lane instead of at the top of the next iteration
-            head = [
-                (0, lambda ln: self._G("generator_A2B", real_A, mask_A, gen_B, self.g_stash1[0], B, ln), (), "gB"),      # :267 generated_B
-                (1, lambda ln: self._G("generator_B2A", real_B, mask_B, gen_A, self.g_stash1[1], B, ln), (), "gA"),      # :259 generated_A
-                (2, clear_g, (), None),
-            ]
-            cycles = [
-                (0, lambda ln: self._G("generator_B2A", gen_B, None, cyc_A, self.g_stash1[0], B, ln), (), None),         # :271 cycled_A
-                (1, lambda ln: self._G("generator_A2B", gen_A, None, cyc_B, self.g_stash1[1], B, ln), (), None),         # :263 cycled_B
-            ]
-            if B >= self.split_d_min_batch:
-                # The real halves need nothing from the generators: lanes 2/3 run them while lanes 0/1 are in the generator forwards, so the
-                # tail of the phase (second-step discriminators behind the cycle forwards) is a pass over the generated half only.  A
-                # discriminator's two passes add into the same gradients: same lane, or ordered by an event.
-                def half(name, fake):
-                    i = idx[name]
-                    sl = slice(B, B2) if fake else slice(0, B)
-                    st = ds[i] if fake else self.d_stash1[i]
-
-                    def run(ln):
-                        self._D(name, di[name][sl], do[i][sl], st, B, ln)
-                        self._lsgan(do[i][sl], 0.0 if fake else 1.0, 0.25, 8 + 2 * i + int(fake), dl[i][sl])
-                        self._D_bwd(name, dl[i][sl], None, 0, st, True, B, ln)
-                    return run
-                tasks = head + [
-                    (2, half("discriminator_A", False), (), None),
-                    (3, half("discriminator_B", False), (), None),
-                    (2, half("discriminator_A2", False), (), "rA2"),
-                    (3, half("discriminator_B2", False), (), "rB2"),
-                ] + cycles + [
-                    (2, half("discriminator_A", True), ("gA",), None),
-                    (3, half("discriminator_B", True), ("gB",), None),
-                    (0, half("discriminator_A2", True), ("rA2",), None),
-                    (1, half("discriminator_B2", True), ("rB2",), None),
-                ]
-            else:
-                tasks = head + cycles + [
-                    (2, disc("discriminator_A"), ("gA",), None),
-                    (3, disc("discriminator_B"), ("gB",), None),
-                    (0, disc("discriminator_A2"), (), None),
-                    (1, disc("discriminator_B2"), (), None),
-                ]
-        else:
-            # (phase called on its own: a lane re-packs the generator it runs first; the other lane's second pass waits for that re-pack)
-            tasks = [
-                (0, lambda ln: self._repack1("generator_B2A"), (), "p0"),
-                (1, lambda ln: self._repack1("generator_A2B"), (), "p1"),
-                (0, lambda ln: self._G("generator_B2A", real_B, mask_B, gen_A, self.g_stash1[0], B, ln), (), "gA"),      # :259 generated_A
-                (1, lambda ln: self._G("generator_A2B", real_A, mask_A, gen_B, self.g_stash1[1], B, ln), (), "gB"),      # :267 generated_B
-                (0, lambda ln: self._G("generator_A2B", gen_A, None, cyc_B, self.g_stash1[0], B, ln), ("p1",), None),    # :263 cycled_B
-                (1, lambda ln: self._G("generator_B2A", gen_B, None, cyc_A, self.g_stash1[1], B, ln), ("p0",), None),    # :271 cycled_A
-                (2, disc("discriminator_A"), ("gA",), None),
-                (3, disc("discriminator_B"), ("gB",), None),
-                (0, disc("discriminator_B2"), (), None),
-                (1, disc("discriminator_A2"), (), None),
-            ]
-        self._run_tasks(tasks)
-        self._combine(8, self._comb_d)
 
     def discriminator_update(self):
         """train.py:299.  With more than one rank the all-reduce is only *started* here; the optimizer step runs when the discriminators

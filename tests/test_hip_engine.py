@@ -97,7 +97,7 @@ def test_lr_decay_bug_and_identity_cutoff_match_reference(golden_dir, determinis
 
 def test_four_iterations_past_the_identity_cutoff_pipelined_and_unflushed(golden_dir, deterministic_mode):
     """The regime a canonical run spends > 97 % of its life in (train.py:314-315: identity_loss_lambda = 0 from then on; :207-210 keeps
-    computing the identity forwards, which the engine drops as dead work -- ``ident_dead`` in engine._g_parts), pinned to the REFERENCE:
+    computing the identity forwards, which the engine drops as dead work -- ``nbt`` in engine._bind_plain), pinned to the REFERENCE:
     the ``cutoff`` fixture is four iterations of the unmodified train() at bs=2 whose iterations 2 and 3 run with lambda_id == 0.
     Replayed through the DEFAULT schedule -- grouped launches, iteration t's discriminator phase pipelined beside iteration t+1's
     generator phase -- with NO flush() between the steps: losses are read the way the training loop reads them (``lagged=True``), the
