@@ -33,7 +33,8 @@ extern "C" {
 #define MCVC_ABI_VERSION 3          /* r4: + mcvc_gen_backward_prefix, mcvc_set_trunk_passes_in_flight, op-level Winograd / staged-GEMM / trunk entries;
                                        3: + mcvc_gen_update_ranges / mcvc_disc_update_batch (optimizer step fused with the re-pack).
                                        Stays 3 where symbols, flag bits or argument values are only ADDED and every existing call keeps its
-                                       meaning (MCVC_BWD_STORE_GRADS, mcvc_disc_backward_flags, mcvc_grad_store_mask, zero_grads == 2) */
+                                       meaning (MCVC_BWD_STORE_GRADS, mcvc_disc_backward_flags, mcvc_grad_store_mask, zero_grads == 2,
+                                       mcvc_net_layout) */
 #define MCVC_GEN_NPARAMS 110
 #define MCVC_DISC_NPARAMS 20
 #define MCVC_N_MEL 80
@@ -337,6 +338,16 @@ int mcvc_disc_update_batch(const float* const* params, const long long* numel, f
  *   5  one of their classes: index, class, nth, ntw, khmax, kwmax, pad_h, pad_w, qh, qw, su, sv, offset
  * *n_rows = rows of the plan; MCVC_ERR_WORKSPACE when cap is smaller (the first cap rows are written), MCVC_ERR_INVALID as the entries. */
 int mcvc_pack_plan(int net, int max_batch, int T, int sets, int range_mask, int update, long long* rows, int cap, int* n_rows);
+/* Host view of the stash and scratch layouts of a (B, T) pass (pure host code, no device call): net 0 the generator, 1 the discriminator.
+ * stash_B / stash_b0 as mcvc_gen_backward_window: the stash was written by a forward pass over stash_B samples (0 = B) and the pass walks
+ * the samples [stash_b0, stash_b0 + B) of it; the discriminator has no windows (stash_B = 0 or B, stash_b0 = 0).  Rows of 12 64-bit integers:
+ *   1  stash tensor, in stash order:  id, offset, floats (of all stash_B samples), N, C, H, W, sample / channel / row stride as the
+ *      backward pass addresses it, offset of the window's first sample
+ *   2  scratch buffer up to the slabs: the same columns (N .. strides = 0 for the untyped ping-pong buffers and workspaces)
+ *   3  last row: 0, then the dry run's conv-slab, weight-gradient-slab, staging and weight-staging floats and the slab offset
+ * Offsets are multiples of 4 floats; a row ends where the next begins (floats rounded up to 4), the last stash row at mcvc_*_stash_floats,
+ * the last scratch row at the slab offset.  *n_rows / cap / return value as mcvc_pack_plan.                                              */
+int mcvc_net_layout(int net, int B, int T, int stash_B, int stash_b0, long long* rows, int cap, int* n_rows);
 int mcvc_axpy(float* y, const float* x, float alpha, long long n, void* stream);
 
 /* ---- on-device input pipeline: replaces VCDataset.__getitem__ + DataLoader collate + 4 H2D copies per iteration

@@ -46,9 +46,47 @@ namespace {
 
 constexpr float kInEps = 1e-5f;
 
-struct View { float* p; long long sb, sc; int sh; };
-struct CView { const float* p; long long sb, sc; int sh; };
-static inline CView cv(const View& v) { return CView{v.p, v.sb, v.sc, v.sh}; }
+// A tensor as the kernels address it: N samples of C channels of H x W, sample / channel / row strides in floats (columns contiguous).
+// The layouts the passes use are the named constructors below, each written once; what a wrapper needs beside the pointer -- the
+// sample count, the image size, the dense size that spaces K-split slabs -- it reads off the tensor.
+enum Layout { L_STRIDED, L_PHASE_SPLIT, L_PADDED_DY };
+template <class T> struct TensorT {
+    T* p; int N, C, H, W; long long sb, sc; int sh; Layout lay;
+    operator TensorT<const T>() const { return {p, N, C, H, W, sb, sc, sh, lay}; }
+    int P() const { return H * W; }
+    long long dense() const { return (long long)N * C * H * W; }                 // slab stride of a K split that writes this tensor
+    TensorT at(T* q) const { TensorT t = *this; t.p = q; return t; }             // the same shape elsewhere
+    TensorT channels(int c0, int n) const { TensorT t = *this; t.p = p + c0 * sc; t.C = n; return t; }
+    TensorT samples(int b0, int n) const { TensorT t = *this; t.p = p + b0 * sb; t.N = n; return t; }
+    // trunk layout only: the B rows of a channel as ONE image of B rows (every Conv1d is a single-image convolution) ...
+    TensorT image() const { return {p, 1, C, N, W, 0, sc, sh, lay}; }
+    // ... and 20 consecutive channels as the rows of one (channel = c * 20 + h: the reference's view(B, 5120, 1, -1))
+    TensorT rows20() const { return {p, N, C / 20, 20, W, sb, 20 * sc, (int)sc, lay}; }
+    // dense planes only: every row a channel of its own (H x W -> H channels of 1 x W)
+    TensorT rows_as_channels() const { return {p, N, C * H, 1, W, sb, (long long)sh, sh, lay}; }
+};
+using Tensor = TensorT<float>;
+using CTensor = TensorT<const float>;
+// dense, batch-major [N][C][H][W]
+template <class T> static TensorT<T> nchw(T* p, int N, int C, int H, int W) { return {p, N, C, H, W, (long long)C * H * W, (long long)H * W, W, L_STRIDED}; }
+// a dense buffer of n floats as one row (the in-place slab sums of the op-level entries)
+template <class T> static TensorT<T> flat(T* p, long long n) { return nchw(p, 1, 1, 1, (int)n); }
+// 1-D trunk layout [C][rows][W4], per sample: B samples W4 apart; channel pitch = rows x W4 of the buffer (the stash's rows: stash_B)
+template <class T> static TensorT<T> trunk_rows(T* p, int B, int C, int W4, long long pitch) { return {p, B, C, 1, W4, (long long)W4, pitch, W4, L_STRIDED}; }
+// input of a 3x3 stride-2 layer in the phase-split padded layout (sgemm.h): four padded phase planes per channel; H x W = the image
+template <class T> static TensorT<T> phase_split(T* p, int N, int C, int H, int W)
+{ const long long pl = mcvc_xs_plane(H, W); return {p, N, C, H, W, C * 4 * pl, 4 * pl, W, L_PHASE_SPLIT}; }
+// dY of such a layer in the padded layout its implicit data gradient gathers from: planes of (OH + 1) rows of OW + 4 floats
+template <class T> static TensorT<T> padded_dy(T* p, int N, int C, int OH, int OW)
+{ const long long pl = mcvc_dyp_plane(OH, OW); return {p, N, C, OH, OW, C * pl, pl, mcvc_dyp_pitch(OW), L_PADDED_DY}; }
+// the direct kernels' operands
+static ConvIO conv_io(CTensor x, Tensor y)
+{
+    ConvIO io{};
+    io.x = x.p; io.x_sb = x.sb; io.x_sc = x.sc; io.x_sh = x.sh;
+    io.y = y.p; io.y_sb = y.sb; io.y_sc = y.sc; io.y_sh = y.sh; io.y_sw = 1;
+    return io;
+}
 
 constexpr int kMaxLayers = 20;
 struct PackFresh { unsigned layer[kMaxLayers]; PackFresh() { for (unsigned& m : layer) m = kAllForms; } };
@@ -80,9 +118,6 @@ struct Exec {
     int fuse_next = 0;             // the caller's next step is a norm that can absorb a Winograd output transform (set before conv_fwd)
     const struct WinoFam* pend_fam = nullptr;   // the output transform of this family in `pend` has not run yet -- norm_fwd runs it (fused when it fits)
     WinoOutArgs pend;
-    int y_xs_pw = 0; long long y_xs_plane = 0;   // the next norm_fwd writes y in the phase-split padded layout (sgemm.h); consumed by norm_fwd
-    int dx_pitch = 0;              // the next norm_bwd writes dx in the padded dY layout (rows of dx_pitch floats + a zero row); consumed by norm_bwd
-    int wgrad_x_xs = 0;            // conv_wgrad: x is in the phase-split padded layout
     int store_grads = 0;           // backward pass: the weight gradients of the covered layers are STORED (MCVC_BWD_STORE_GRADS; conv_wgrad)
     int force_scheme = 0;          // op-level entries (mcvc_layer_*): 0 planner's choice, 1 Winograd with 2x2 output tiles only, 2 with 4x4 tiles
                                    // (thresholds on samples / tiles lifted), 3 no Winograd, 4 no Winograd and no staged GEMM (direct kernels)
@@ -140,6 +175,16 @@ static void wait_readers(Exec& ex, const void* buf)
         if (it->first == buf) { ex.fail(mcvc_stream_wait(ex.s, it->second)); it = ex.readers.erase(it); }
         else ++it;
     }
+}
+
+// the stream for work that runs beside the main chain: the auxiliary stream, made to wait for everything issued on the main stream so far
+static hipStream_t fork_aux(Exec& ex)
+{
+    if (!ex.s2) return ex.s;
+    hipEvent_t e = pool_event();
+    ex.fail(mcvc_event_record(e, ex.s));
+    ex.fail(mcvc_stream_wait(ex.s2, e));
+    return ex.s2;
 }
 
 static void join_aux(Exec& ex)
@@ -330,7 +375,7 @@ struct WinoPass {
     int shuffle, YH, YW, accumulate;                    // the store (WinoOutArgs)
     bool may_defer;                                     // the output transform may be left to the next norm_fwd
 };
-static void wino_pass(Exec& ex, const WinoPass& p, CView x, View y)
+static void wino_pass(Exec& ex, const WinoPass& p, CTensor x, Tensor y)
 {
     const WinoFam& f = *p.f;
     const int K = p.K, M = p.M, TH = (p.H + f.tile - 1) / f.tile, TW = (p.W + f.tile - 1) / f.tile;
@@ -338,7 +383,7 @@ static void wino_pass(Exec& ex, const WinoPass& p, CView x, View y)
         const int nb = p.NB - b0 < p.nbc ? p.NB - b0 : p.nbc;
         const long long NT = (long long)nb * TH * TW, NTp = std::max<long long>((NT + 31) & ~31LL, f.min_pitch);
         WinoXformArgs xi{};
-        xi.x = x.p + (long long)b0 * x.sb; xi.x_sb = x.sb; xi.x_sc = x.sc; xi.x_sh = x.sh; xi.v = ex.wv;
+        xi.x = x.samples(b0, nb).p; xi.x_sb = x.sb; xi.x_sc = x.sc; xi.x_sh = x.sh; xi.v = ex.wv;
         xi.N = nb; xi.C = K; xi.H = p.H; xi.W = p.W; xi.TH = TH; xi.TW = TW; xi.NT = (int)NT; xi.NTp = (int)NTp; xi.pad = f.pad;
         ex.fail(p.XH ? f.input_phase(xi, p.XH, p.XW, ex.s) : f.input(xi, ex.s));
         static const int own_gemm = mcvc_knob("MCVC_WINO_GEMM", 1);
@@ -353,9 +398,7 @@ static void wino_pass(Exec& ex, const WinoPass& p, CView x, View y)
             // F(2x2,5x5) outside the GEMM's shapes: one launch of the direct-conv kernel as a 1x1 conv over 36 images with per-image weights;
             // the 36 products see the tiles as a (NTp/32) x 32 "image" so that the conv kernel's 2-D pixel tiles are full
             ConvProblem cp{K, (int)(NTp / 32), 32, M, (int)(NTp / 32), 32, 1, 1, 1, 0, 0};
-            ConvIO io{};
-            io.x = ex.wv; io.x_sb = (long long)K * NTp; io.x_sc = NTp; io.x_sh = 32;
-            io.y = ex.wm; io.y_sb = (long long)M * NTp; io.y_sc = NTp; io.y_sh = 32; io.y_sw = 1;
+            ConvIO io = conv_io(nchw(ex.wv, 36, K, (int)(NTp / 32), 32), nchw(ex.wm, 36, M, (int)(NTp / 32), 32));
             io.nsplit = 1;
             io.w_nstride = p.a_xi;
             io.tile_cfg = wino_tile_cfg(M, NT);
@@ -364,7 +407,7 @@ static void wino_pass(Exec& ex, const WinoPass& p, CView x, View y)
         }
         WinoOutArgs oa{};
         oa.m = ex.wm; oa.bias = p.bias;
-        oa.y = y.p + (long long)b0 * y.sb; oa.y_sb = y.sb; oa.y_sc = y.sc; oa.y_sh = y.sh;
+        oa.y = y.samples(b0, nb).p; oa.y_sb = y.sb; oa.y_sc = y.sc; oa.y_sh = y.sh;
         oa.N = nb; oa.Cout = M; oa.OH = p.H; oa.OW = p.W; oa.TH = TH; oa.TW = TW; oa.NT = (int)NT; oa.NTp = (int)NTp;
         oa.shuffle = p.shuffle; oa.YH = p.YH; oa.YW = p.YW; oa.accumulate = p.accumulate;
         if (p.may_defer && ex.fuse_next && p.nbc == p.NB) { ex.pend = oa; ex.pend_fam = &f; }
@@ -377,21 +420,21 @@ static void wino_pass(Exec& ex, const WinoPass& p, CView x, View y)
 // gradient instead of adding to what dw held, the later ones add to it).  A stride-2 layer runs in the phase
 // formulation (see conv_wino3): dU[xi][co][4ci+2p+q], both branches (value | gate) in one product, the 3x3 blocks scattered back into the two
 // 5x5 gradients.
-static void wino_wgrad_pass(Exec& ex, const WinoFam& f, const ConvSpec& c, float* const* grads, int NB, int nbc, int H, int W, CView x, CView dy,
-                            int store, hipStream_t ws)
+static void wino_wgrad_pass(Exec& ex, const WinoFam& f, const ConvSpec& c, float* const* grads, int nbc, CTensor x, CTensor dy, int store, hipStream_t ws)
 {
     const bool phase = c.stride == 2;
+    const int NB = x.N, H = x.H, W = x.W;
     const int IH = phase ? H / 2 : H, IW = phase ? W / 2 : W, N = phase ? 4 * c.Cin : c.Cin, M = c.cout_tot;
     const int TH = (IH + f.tile - 1) / f.tile, TW = (IW + f.tile - 1) / f.tile;
     for (int b0 = 0; b0 < NB; b0 += nbc) {
         const int nb = NB - b0 < nbc ? NB - b0 : nbc;
         const long long NT = (long long)nb * TH * TW, NTp = (NT + 31) & ~31LL;
         WinoXformArgs xi{};
-        xi.x = x.p + (long long)b0 * x.sb; xi.x_sb = x.sb; xi.x_sc = x.sc; xi.x_sh = x.sh; xi.v = ex.wv2;
+        xi.x = x.samples(b0, nb).p; xi.x_sb = x.sb; xi.x_sc = x.sc; xi.x_sh = x.sh; xi.v = ex.wv2;
         xi.N = nb; xi.C = N; xi.H = IH; xi.W = IW; xi.TH = TH; xi.TW = TW; xi.NT = (int)NT; xi.NTp = (int)NTp; xi.pad = f.pad;
         ex.fail(phase ? f.input_phase_t(xi, H, W, ws) : f.input_t(xi, ws));
         WinoXformArgs di{};
-        di.x = dy.p + (long long)b0 * dy.sb; di.x_sb = dy.sb; di.x_sc = dy.sc; di.x_sh = dy.sh; di.v = ex.wm2;
+        di.x = dy.samples(b0, nb).p; di.x_sb = dy.sb; di.x_sc = dy.sc; di.x_sh = dy.sh; di.v = ex.wm2;
         di.N = nb; di.C = M; di.H = IH; di.W = IW; di.TH = TH; di.TW = TW; di.NT = (int)NT; di.NTp = (int)NTp; di.pad = 0;
         ex.fail(f.dy_t(di, ws));
         WinoGemmArgs ga{};
@@ -406,10 +449,10 @@ static void wino_wgrad_pass(Exec& ex, const WinoFam& f, const ConvSpec& c, float
 }
 
 // 5x5 stride-1 conv (upSample1/2; see above wino4_min_nb): F(4x4,5x5) where it applies, else F(2x2,5x5)
-static bool conv_wino(Exec& ex, const ConvSpec& c, const float* packed, int dgrad, int NB, int H, int W, CView x, View y, int shuffle,
-                      int accumulate)
+static bool conv_wino(Exec& ex, const ConvSpec& c, const float* packed, int dgrad, CTensor x, Tensor y, int shuffle, int accumulate)
 {
     if (!c.wino || !wino_enabled() || !ex.wv) return false;
+    const int NB = x.N, H = dgrad ? y.H : x.H, W = dgrad ? y.W : x.W;          // the convolution's input image: x, or the dX a data gradient writes
     const int K = dgrad ? c.cout_tot : c.Cin, M = dgrad ? c.Cin : c.cout_tot;
     const WinoFam* f = &kWino[kF45];
     int nbc = 0;
@@ -439,9 +482,10 @@ static bool conv_wino(Exec& ex, const ConvSpec& c, const float* packed, int dgra
 // Forward (H, W even): over the four input phases, K = 4*Cin.  dgrad: the merged data gradient = a conv over dY with 4*Cin output channels and a
 // PixelShuffle store into dX; x is dY and y is dX there.  (c.wino3 says 4*Cin % 128 == 0 and cout_tot % 16 == 0: the GEMM's shapes hold for
 // the data gradient; these layers' OH x OW is ceil(H/2) x ceil(W/2), what the merged form stores.)
-static bool conv_wino3(Exec& ex, const ConvSpec& c, const float* packed, int dgrad, int NB, int H, int W, CView x, View y, int accumulate)
+static bool conv_wino3(Exec& ex, const ConvSpec& c, const float* packed, int dgrad, CTensor x, Tensor y, int accumulate)
 {
     if (!c.wino3 || !wino_enabled() || !ex.wv) return false;
+    const int NB = x.N, H = dgrad ? y.H : x.H, W = dgrad ? y.W : x.W;
     if (!dgrad && ((H & 1) != 0 || (W & 1) != 0 || (c.cout_tot % 128) != 0)) return false;
     static const int en[2] = {mcvc_knob("MCVC_WINO3_FWD", 1), mcvc_knob("MCVC_WINO3", 1)};
     if (!en[dgrad]) return false;
@@ -535,13 +579,13 @@ static void xs_tap_offsets(int H, int W, long long boff[9])
 // K split: enough 64 x 64 tiles x classes x splits to occupy the chip, at least two 32-deep stages per split of the shortest class
 static int igemm_split(long long tiles, int Kmin) { return split_by_cost(tiles, Kmin); }
 // forward: xs = the input in the phase-split padded layout, y = the conv output (dense planes); K-split slabs 1.. are summed by the consumer
-static void conv_fwd_igemm(Exec& ex, const ConvSpec& c, const float* packed, int NB, int H, int W, const float* xs, View y, long long y_total,
-                           int allow_split, int* nsplit)
+static void conv_fwd_igemm(Exec& ex, const ConvSpec& c, const float* packed, CTensor xs, Tensor y, int allow_split, int* nsplit)
 {
+    const int NB = xs.N, H = xs.H, W = xs.W;
     const int OH = H / 2, OW = W / 2, P = OH * OW, KT = 9 * c.Cin;
     const long long NT = (long long)NB * P;
     const int sp = (allow_split && nsplit) ? igemm_split((long long)(c.cout_tot / 64) * ((NT + 63) / 64), KT) : 1;
-    const long long slab_need = (long long)(sp - 1) * y_total;
+    const long long slab_need = (long long)(sp - 1) * y.dense();
     if (slab_need > ex.slab_need) ex.slab_need = slab_need;
     if (nsplit) *nsplit = sp;
     if (ex.dry) return;
@@ -554,24 +598,24 @@ static void conv_fwd_igemm(Exec& ex, const ConvSpec& c, const float* packed, int
     xs_tap_offsets(H, W, g.cls[0].boff);
     for (int t = 0; t < 9; ++t) g.cls[0].aoff[t] = (long long)t * c.Cin * c.cout_pk;      // tap-major copy: rows (tap, ci)
     g.a_ks = c.cout_pk;
-    g.b = xs; g.b_cs = 4 * plane; g.b_sn = (long long)c.Cin * 4 * plane; g.b_pitch = pw; g.Cb = c.Cin; g.OW = OW; g.P = P;
+    g.b = xs.p; g.b_cs = 4 * plane; g.b_sn = (long long)c.Cin * 4 * plane; g.b_pitch = pw; g.Cb = c.Cin; g.OW = OW; g.P = P;
     g.c = y.p; g.ldc = y.sc; g.c_sn = y.sb; g.c_sh = y.sh; g.c_sw = 1;
     g.bias = packed + c.off[PF_BIAS];
-    g.M = c.cout_tot; g.N = (int)NT; g.nsplit = sp; g.c_slab = ex.slabs; g.c_split = y_total;
+    g.M = c.cout_tot; g.N = (int)NT; g.nsplit = sp; g.c_slab = ex.slabs; g.c_split = y.dense();
     ex.fail(mcvc_igemm_launch(g, ex.s));
 }
 // data gradient: dyp = dY in the padded layout (planes of (OH + 1) x (OW + 4), zero borders), dx dense; the four output-parity classes in
 // one launch, every input pixel written by exactly one of them; K-split slabs (dx-shaped) are summed by the consumer
-static void conv_dgrad_igemm(Exec& ex, const ConvSpec& c, const float* packed, int NB, int H, int W, const float* dyp, View dx, long long dx_total,
-                             int accumulate, int allow_split, int* nsplit)
+static void conv_dgrad_igemm(Exec& ex, const ConvSpec& c, const float* packed, CTensor dyp, Tensor dx, int accumulate, int allow_split, int* nsplit)
 {
+    const int NB = dx.N, H = dx.H, W = dx.W;
     const int OH = H / 2, OW = W / 2, P = OH * OW;
     const long long NT = (long long)NB * P;
     int sp = (allow_split && nsplit && !accumulate) ? igemm_split(4LL * (c.Cin / 64) * ((NT + 63) / 64), c.cout_tot) : 1;
     // (Tried on top, r5: deeper uniform splits -- 4-tap class at most 512 deep -- and tap-wise splits with zero-filled slabs for the classes with
     //  fewer taps, so that every workgroup is one tap deep: bs=1 6.01 -> 6.03-6.12 and -> 6.3 ms.  The consumer reading 4-8 slabs costs more
     //  than the imbalance of the classes; the uniform split of r4 stays.)
-    const long long slab_need = (long long)(sp - 1) * dx_total;
+    const long long slab_need = (long long)(sp - 1) * dx.dense();
     if (slab_need > ex.slab_need) ex.slab_need = slab_need;
     if (nsplit) *nsplit = sp;
     if (ex.dry) return;
@@ -593,22 +637,22 @@ static void conv_dgrad_igemm(Exec& ex, const ConvSpec& c, const float* packed, i
             }
     }
     g.a_ks = c.cout_pk; g.arow = 1;
-    g.b = dyp; g.b_cs = plane; g.b_sn = (long long)c.cout_tot * plane; g.b_pitch = pitch; g.Cb = c.cout_tot; g.OW = OW; g.P = P;
+    g.b = dyp.p; g.b_cs = plane; g.b_sn = (long long)c.cout_tot * plane; g.b_pitch = pitch; g.Cb = c.cout_tot; g.OW = OW; g.P = P;
     g.c = dx.p; g.ldc = dx.sc; g.c_sn = dx.sb; g.c_sh = 2 * dx.sh; g.c_sw = 2; g.accumulate = accumulate;
-    g.M = c.Cin; g.N = (int)NT; g.nsplit = sp; g.c_slab = ex.slabs; g.c_split = dx_total;
+    g.M = c.Cin; g.N = (int)NT; g.nsplit = sp; g.c_slab = ex.slabs; g.c_split = dx.dense();
     ex.fail(mcvc_igemm_launch(g, ex.s));
 }
 
-static void conv_fwd(Exec& ex, const ConvSpec& c, const float* packed, int NB, int H, int W, CView x, View y, long long y_total,
-                     int shuffle, int allow_split, int* nsplit)
+static void conv_fwd(Exec& ex, const ConvSpec& c, const float* packed, CTensor x, Tensor y, int shuffle, int allow_split, int* nsplit)
 {
+    const int NB = x.N, H = x.H, W = x.W;          // (y describes the buffer as stored: behind a PixelShuffle, C / 4 channels of 2H x 2W)
     const SgKind sk = shuffle ? SgKind{0, 0, 0, 0} : sgemm_kind(c, NB, H, W);
     if (sk.kind) {
         const int P = sk.OH * sk.OW, KT = sk.taps * c.Cin;
         const long long NT = (long long)NB * P;
         const bool b_in_place = c.KW == 1;                                                    // a 1x1 conv multiplies x itself
         const int sp = (allow_split && nsplit) ? sgemm_split(c.cout_tot, NT, KT) : 1;       // slabs 1.. are summed by the consumer (norm / act)
-        const long long slab_need = (long long)(sp - 1) * y_total;
+        const long long slab_need = (long long)(sp - 1) * y.dense();
         if (ex.dry) { if (slab_need > ex.slab_need) ex.slab_need = slab_need; if (nsplit) *nsplit = sp; return; }
         if (stale(ex, c, PF_FWD)) return;
         if (!b_in_place && slab_need <= ex.slab_cap && y.sh == sk.OW && y.sc == P && (NB == 1 || y.sb == (long long)c.cout_tot * P)) {
@@ -623,7 +667,7 @@ static void conv_fwd(Exec& ex, const ConvSpec& c, const float* packed, int NB, i
             g.b = x.p; g.b_cs = x.sc; g.b_sn = x.sb; g.b_pitch = x.sh; g.Cb = c.Cin; g.OW = W; g.P = P;
             g.c = y.p; g.ldc = y.sc; g.c_sn = y.sb; g.c_sh = y.sh; g.c_sw = 1;
             g.bias = packed + c.off[PF_BIAS];
-            g.M = c.cout_tot; g.N = (int)NT; g.nsplit = sp; g.c_slab = ex.slabs; g.c_split = y_total;
+            g.M = c.cout_tot; g.N = (int)NT; g.nsplit = sp; g.c_slab = ex.slabs; g.c_split = y.dense();
             ex.fail(mcvc_igemm_launch(g, ex.s));
             if (nsplit) *nsplit = sp;
             return;
@@ -635,28 +679,26 @@ static void conv_fwd(Exec& ex, const ConvSpec& c, const float* packed, int NB, i
             g.b = x.p; g.ldb = x.sc; g.bseg = P; g.b_sn = x.sb;
             g.c = y.p; g.ldc = y.sc; g.cseg = P; g.c_sn = y.sb;
             g.bias = packed + c.off[PF_BIAS];
-            g.M = c.cout_tot; g.N = (int)NT; g.K = KT; g.nsplit = sp; g.c_slab = ex.slabs; g.c_split = y_total;
+            g.M = c.cout_tot; g.N = (int)NT; g.K = KT; g.nsplit = sp; g.c_slab = ex.slabs; g.c_split = y.dense();
             ex.fail(mcvc_sgemm_launch(g, ex.s));
             if (nsplit) *nsplit = sp;
             return;
         }
     }
-    if (conv_wino(ex, c, packed, 0, NB, H, W, x, y, shuffle, 0) || (!shuffle && conv_wino3(ex, c, packed, 0, NB, H, W, x, y, 0))) { if (nsplit) *nsplit = 1; return; }
+    if (conv_wino(ex, c, packed, 0, x, y, shuffle, 0) || (!shuffle && conv_wino3(ex, c, packed, 0, x, y, 0))) { if (nsplit) *nsplit = 1; return; }
     if (stale(ex, c, PF_FWD)) return;          // the direct kernels are next
     ConvProblem p{c.Cin, H, W, c.cout_tot, conv_out(H, c.KH, c.stride, c.ph), conv_out(W, c.KW, c.stride, c.pw),
                   c.KH, c.KW, c.stride, c.ph, c.pw};
-    ConvIO io{};
-    io.x = x.p; io.x_sb = x.sb; io.x_sc = x.sc; io.x_sh = x.sh;
-    io.y = y.p; io.y_sb = y.sb; io.y_sc = y.sc; io.y_sh = y.sh; io.y_sw = 1;
+    ConvIO io = conv_io(x, y);
     io.shuffle = shuffle;
-    run_conv(ex, p, NB, io, y_total, packed + c.off[PF_FWD], c.w_rows, c.cout_pk, packed + c.off[PF_BIAS], allow_split, 0, nsplit);
+    run_conv(ex, p, NB, io, y.dense(), packed + c.off[PF_FWD], c.w_rows, c.cout_pk, packed + c.off[PF_BIAS], allow_split, 0, nsplit);
 }
 
 // dX = conv-backward-data.  dy: conv-output layout (cout_tot channels, OHxOW); dx: input layout.
-static void conv_dgrad(Exec& ex, const ConvSpec& c, const float* packed, int NB, int H, int W, CView dy, View dx, long long dx_total,
-                       int accumulate, int allow_split, int* nsplit)
+static void conv_dgrad(Exec& ex, const ConvSpec& c, const float* packed, CTensor dy, Tensor dx, int accumulate, int allow_split, int* nsplit)
 {
-    if (conv_wino(ex, c, packed, 1, NB, H, W, dy, dx, 0, accumulate)) { if (nsplit) *nsplit = 1; return; }
+    const int NB = dx.N, H = dx.H, W = dx.W;
+    if (conv_wino(ex, c, packed, 1, dy, dx, 0, accumulate)) { if (nsplit) *nsplit = 1; return; }
     const int OH = conv_out(H, c.KH, c.stride, c.ph), OW = conv_out(W, c.KW, c.stride, c.pw);
     const int st = c.stride;
     const SgKind sk = sgemm_kind(c, NB, H, W);
@@ -669,7 +711,7 @@ static void conv_dgrad(Exec& ex, const ConvSpec& c, const float* packed, int NB,
         int sp = (allow_split && nsplit) ? igemm_split((long long)(c.Cin / 64) * ((NT + 63) / 64), sk.taps * c.cout_tot) : 1;
         while (sp > 1 && ((long long)sk.taps * c.cout_tot) % (32LL * sp) != 0) sp /= 2;
         const bool slab_all = accumulate && sp > 1;
-        const long long slab_need = (long long)(slab_all ? sp : sp - 1) * dx_total;
+        const long long slab_need = (long long)(slab_all ? sp : sp - 1) * dx.dense();
         if (slab_need > ex.slab_need) ex.slab_need = slab_need;
         if (nsplit) *nsplit = slab_all ? sp + 1 : sp;
         if (ex.dry) return;
@@ -686,23 +728,21 @@ static void conv_dgrad(Exec& ex, const ConvSpec& c, const float* packed, int NB,
         g.a_ks = (long long)c.KW * c.cout_pk; g.arow = 1; g.zw = W;
         g.b = dy.p; g.b_cs = dy.sc; g.b_sn = dy.sb; g.b_pitch = dy.sh; g.Cb = c.cout_tot; g.OW = W; g.P = P;
         g.ldc = dx.sc; g.c_sn = dx.sb; g.c_sh = dx.sh; g.c_sw = 1;
-        g.M = c.Cin; g.N = (int)NT; g.nsplit = sp; g.c_split = dx_total;
-        if (slab_all) { g.c = ex.slabs; g.c_slab = ex.slabs + dx_total; }
+        g.M = c.Cin; g.N = (int)NT; g.nsplit = sp; g.c_split = dx.dense();
+        if (slab_all) { g.c = ex.slabs; g.c_slab = ex.slabs + dx.dense(); }
         else { g.c = dx.p; g.c_slab = ex.slabs; g.accumulate = accumulate; }
         ex.fail(mcvc_igemm_launch(g, ex.s));
         return;
     }
-    if (conv_wino3(ex, c, packed, 1, NB, H, W, dy, dx, accumulate)) { if (nsplit) *nsplit = 1; return; }
+    if (conv_wino3(ex, c, packed, 1, dy, dx, accumulate)) { if (nsplit) *nsplit = 1; return; }
     static const int ucls_nb = mcvc_knob("MCVC_DGRAD_CLASSES_NB", 8);
     const bool per_class = c.merged && c.off[PF_DCLS] >= 0 && NB >= ucls_nb;
     if (stale(ex, c, per_class ? PF_DCLS : PF_DGRAD)) return;          // the direct kernels are next
     if (c.merged && !per_class) {
         ConvProblem p{c.cout_tot, OH, OW, 4 * c.Cin, (H + 1) / 2, (W + 1) / 2, c.mg_kh, c.mg_kw, 1, c.mg_pad_h, c.mg_pad_w};
-        ConvIO io{};
-        io.x = dy.p; io.x_sb = dy.sb; io.x_sc = dy.sc; io.x_sh = dy.sh;
-        io.y = dx.p; io.y_sb = dx.sb; io.y_sc = dx.sc; io.y_sh = dx.sh; io.y_sw = 1;
+        ConvIO io = conv_io(dy, dx);
         io.accumulate = accumulate; io.shuffle = 1; io.YH = H; io.YW = W;
-        run_conv(ex, p, NB, io, dx_total, packed + c.off[PF_DGRAD], c.dg_rows_co * c.mg_kh * c.mg_kw, c.mg_ld, nullptr, allow_split, 0, nsplit);
+        run_conv(ex, p, NB, io, dx.dense(), packed + c.off[PF_DGRAD], c.dg_rows_co * c.mg_kh * c.mg_kw, c.mg_ld, nullptr, allow_split, 0, nsplit);
         return;
     }
     const DgradClass* klass = per_class ? c.ucls : c.cls;
@@ -724,15 +764,14 @@ static void conv_dgrad(Exec& ex, const ConvSpec& c, const float* packed, int NB,
     for (int k = 0; k < c.ncls; ++k) {
         const DgradClass& d = klass[k];
         if (ps[k].OH <= 0 || ps[k].OW <= 0) continue;
-        ConvIO io{};
-        io.x = dy.p; io.x_sb = dy.sb; io.x_sc = dy.sc; io.x_sh = dy.sh;
-        io.y = dx.p + (long long)d.qh * dx.sh + d.qw; io.y_sb = dx.sb; io.y_sc = dx.sc; io.y_sh = dx.sh * st; io.y_sw = st;
+        ConvIO io = conv_io(dy, dx);
+        io.y = dx.p + (long long)d.qh * dx.sh + d.qw; io.y_sh = dx.sh * st; io.y_sw = st;
         io.accumulate = accumulate;
         int ns = 1;
         // slabs of class k live at the same slab base + the class's element offset
         Exec sub = ex;
         if (!ex.dry) sub.slabs = ex.slabs + (long long)d.qh * dx.sh + d.qw;
-        run_conv(sub, ps[k], NB, io, dx_total, packed + kbase + d.offset, c.dg_rows_co * d.nth * d.ntw, c.cin_pk, nullptr,
+        run_conv(sub, ps[k], NB, io, dx.dense(), packed + kbase + d.offset, c.dg_rows_co * d.nth * d.ntw, c.cin_pk, nullptr,
                  allow_split, force, &ns);
         ex.err = sub.err; ex.slab_need = sub.slab_need;
         if (ns > ns_all) ns_all = ns;
@@ -750,13 +789,14 @@ static int wgrad_cin1_enabled()
 // buffer held.  The writers that can store do (the first one of a pass that runs in chunks / slabs; the rest add to it); in front of a
 // writer that can only add -- the direct kernel with slabs or atomics, a fall-back at an odd frame count or without a workspace -- the
 // tensor is zero-filled on the writer's stream.  So correctness never depends on which writer the planner picks, only the speed does.
-static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, int NB, int H, int W, CView x, CView dy)
+static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, CTensor x, CTensor dy)
 {
+    const int NB = x.N, H = x.H, W = x.W;
     const int OH = conv_out(H, c.KH, c.stride, c.ph), OW = conv_out(W, c.KW, c.stride, c.pw);
     ConvProblem p{c.Cin, H, W, c.Cout, OH, OW, c.KH, c.KW, c.stride, c.ph, c.pw};
     // GEMM form (sgemm.h): pixel-major operands in the weight gradients' own staging region, K-split slabs, then dw += slabs
     const SgKind sk = sgemm_kind(c, NB, H, W);                            // (the 1 x KW layers of the wide trunk)
-    const bool ig3 = ex.wgrad_x_xs && igemm_applies(c, H, W);             // a 3 x 3 stride-2 layer whose input arrives phase-split
+    const bool ig3 = x.lay == L_PHASE_SPLIT && igemm_applies(c, H, W);             // a 3 x 3 stride-2 layer whose input arrives phase-split
     const int wtaps = ig3 ? 9 : sk.taps;
     const int KT = wtaps * c.Cin;
     long long sg_floats = 0;
@@ -784,13 +824,7 @@ static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, int NB,
         return;
     }
     if (!grads) return;
-    hipStream_t ws = ex.s;
-    if (ex.s2) {           // dY (and x) are complete on the main stream at this point
-        hipEvent_t e = pool_event();
-        ex.fail(mcvc_event_record(e, ex.s));
-        ex.fail(mcvc_stream_wait(ex.s2, e));
-        ws = ex.s2;
-    }
+    hipStream_t ws = fork_aux(ex);           // dY (and x) are complete on the main stream at this point
     const bool store = ex.store_grads && grad_store_covered(c);
     const long long wnumel = (long long)c.Cout * c.Cin * c.KH * c.KW;
     auto zero_fill = [&](int br, hipStream_t zs) {            // store mode in front of a writer that can only add
@@ -821,7 +855,7 @@ static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, int NB,
         }
         done = true;
     }
-    if (!done && ex.wgrad_x_xs) { ex.fail(MCVC_ERR_WORKSPACE); return; }     // (nothing else reads a phase-split input: never fall through to a dense reader)
+    if (!done && x.lay == L_PHASE_SPLIT) { ex.fail(MCVC_ERR_WORKSPACE); return; }     // (nothing else reads a phase-split input: never fall through to a dense reader)
     if (!done && (c.wino ? c.nbr == 1 : c.wino3 && (H & 1) == 0 && (W & 1) == 0 && (c.nbr == 1 || grads[c.wi[1]])) && wino_enabled() && ex.wu && grads[c.wi[0]]) {
         // Winograd weight gradient (wino_wgrad_pass); the stride-2 layers' 3x3 convolution runs over the phase planes, OH x OW
         static const int en25 = mcvc_knob("MCVC_WINO_WGRAD", 1), en3 = mcvc_knob("MCVC_WINO3_WGRAD", 1);
@@ -829,7 +863,7 @@ static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, int NB,
         auto attempt = [&](const WinoFam& f, int en, int min_tiles) {
             if (!en || (M % 128) != 0 || (N % 64) != 0 || (long long)f.pts * M * N > ex.wu_cap) return false;
             const int nbc = wino_nbc(ex, f, NB, wino_tiles(f, IH, IW), M > N ? M : N, min_tiles);
-            if (nbc) wino_wgrad_pass(ex, f, c, grads, NB, nbc, H, W, x, dy, store, ws);
+            if (nbc) wino_wgrad_pass(ex, f, c, grads, nbc, x, dy, store, ws);
             return nbc != 0;
         };
         // (MCVC_WINO_WGRAD switches the 36-point form only)
@@ -861,8 +895,9 @@ static void conv_wgrad(Exec& ex, const ConvSpec& c, float* const* grads, int NB,
     }
 }
 
-static void conv_bias_grad(Exec& ex, const ConvSpec& c, float* const* grads, int NB, CView dy, int P)
+static void conv_bias_grad(Exec& ex, const ConvSpec& c, float* const* grads, CTensor dy)
 {
+    const int NB = dy.N, P = dy.P();
     if (ex.dry || !grads || !c.has_bias_grad) return;
     for (int br = 0; br < c.nbr; ++br) {
         float* db = grads[c.bi[br]];
@@ -1067,20 +1102,21 @@ static int g_trunk_net = mcvc_knob("MCVC_TRUNK_NET", 1) != 0;
 static bool trunk_net_enabled() { return g_trunk_net != 0; }
 static bool trunk_bwd_net_enabled() { return g_trunk_net == 1; }          // (2 = forward only)
 
-// conv1d + bias + IN (+GLU | +residual); input / conv_out in trunk layout [C][B][W4]; y plane (b, c) at y + b*y_sn + c*y_sc
-static bool trunk_fwd(Exec& ex, const ConvSpec& c, const float* const* P, int g0, int be0, int g1, int be1, const float* x, float* conv_out,
-                      float* stats, float* y, long long y_sn, long long y_sc, const float* res, int B, int W4)
+// conv1d + bias + IN (+GLU | +residual); input / conv_out in trunk layout [C][B][W4]; y plane (b, c) at y.p + b*y.sb + c*y.sc
+static bool trunk_fwd(Exec& ex, const ConvSpec& c, const float* const* P, int g0, int be0, int g1, int be1, CTensor x, Tensor conv_out,
+                      float* stats, Tensor y, const float* res)
 {
+    const int B = x.N, W4 = x.W;
     const int mode = (c.nbr == 2) ? TRUNK_IN_GLU : TRUNK_IN;
     if (!trunk_enabled() || c.KH != 1 || !mcvc_trunk_applies(c.Cin, c.KW, c.Cout, B, W4, mode, 1)) return false;
     if (ex.dry) return true;
     TrunkArgs a{};
     a.a0 = P[c.wi[0]]; a.bias0 = P[c.bi[0]]; a.gamma0 = P[g0]; a.beta0 = P[be0];
     if (c.nbr == 2) { a.a1 = P[c.wi[1]]; a.bias1 = P[c.bi[1]]; a.gamma1 = P[g1]; a.beta1 = P[be1]; }
-    a.x = x; a.x_sc = (long long)B * W4; a.x_sb = W4;
+    a.x = x.p; a.x_sc = x.sc; a.x_sb = x.sb;
     a.Cin = c.Cin; a.KW = c.KW; a.K = c.Cin * c.KW; a.M = c.Cout; a.Mtot = c.cout_tot; a.B = B; a.T4 = W4; a.N = B * W4;
-    a.conv_out = conv_out; a.c_sc = (long long)B * W4; a.c_sb = W4;
-    a.stats = stats; a.y = y; a.res = res; a.y_sn = y_sn; a.y_sc = y_sc; a.eps = kInEps; a.mode = mode;
+    a.conv_out = conv_out.p; a.c_sc = conv_out.sc; a.c_sb = conv_out.sb;
+    a.stats = stats; a.y = y.p; a.res = res; a.y_sn = y.sb; a.y_sc = y.sc; a.eps = kInEps; a.mode = mode;
     ex.fail(mcvc_trunk_launch(a, 1, ex.s));
     return true;
 }
@@ -1109,9 +1145,10 @@ struct TrunkPre {              // fused InstanceNorm backward in front of the da
     int xB;                    // samples per channel of x (0 = the pass's batch; larger: backward over a prefix of the forward pass's samples)
 };
 
-static bool trunk_dgrad(Exec& ex, const ConvSpec& c, const float* packed, const float* dy, float* dx, int accumulate, int B, int W4,
+static bool trunk_dgrad(Exec& ex, const ConvSpec& c, const float* packed, CTensor dy, Tensor dx, int accumulate,
                         int* nsplit = nullptr, const TrunkPre* pre = nullptr)
 {
+    const int B = dx.N, W4 = dx.W;
     if (!trunk_enabled() || c.off[PF_TRUNK_T] < 0) return false;
     int ks = 1;
     if (!accumulate && mcvc_trunk_applies(c.cout_tot, c.KW, c.Cin, B, W4, TRUNK_PLAIN, 1)) ks = 1;
@@ -1130,9 +1167,9 @@ static bool trunk_dgrad(Exec& ex, const ConvSpec& c, const float* packed, const 
     if (ex.dry) return true;
     TrunkArgs a{};
     a.a0 = packed + c.off[PF_TRUNK_T];
-    a.x = dy; a.x_sc = (long long)B * W4; a.x_sb = W4;
+    a.x = dy.p; a.x_sc = dy.sc; a.x_sb = dy.sb;
     a.Cin = c.cout_tot; a.KW = c.KW; a.K = c.cout_tot * c.KW; a.M = c.Cin; a.Mtot = c.Cin; a.B = B; a.T4 = W4; a.N = B * W4;
-    a.conv_out = dx; a.c_sc = (long long)B * W4; a.c_sb = W4; a.accumulate = accumulate; a.mode = TRUNK_PLAIN;
+    a.conv_out = dx.p; a.c_sc = dx.sc; a.c_sb = dx.sb; a.accumulate = accumulate; a.mode = TRUNK_PLAIN;
     a.slabs = ex.slabs; a.slab_stride = tot; a.slab_all = slab_all ? 1 : 0;
     if (pre) {
         a.pre = pre->kind; a.pre_C = (pre->kind == 2) ? c.cout_tot / 2 : c.cout_tot;
@@ -1146,8 +1183,9 @@ static bool trunk_dgrad(Exec& ex, const ConvSpec& c, const float* packed, const 
 
 // K too large for one workgroup (conv2dto1d, K = 5120): K-split workgroups write private slabs (split 0 adds the bias) that
 // the InstanceNorm launch sums -- no atomics, no zero-fill.  Weights are read straight from the OIHW parameter.
-static bool trunk_fwd_ksplit(Exec& ex, const ConvSpec& c, const float* const* P, const float* x, float* conv_out, int B, int W4, int* nsplit)
+static bool trunk_fwd_ksplit(Exec& ex, const ConvSpec& c, const float* const* P, CTensor x, Tensor conv_out, int* nsplit)
 {
+    const int B = x.N, W4 = x.W;
     if (!trunk_enabled() || c.KH != 1 || c.nbr != 1) return false;
     const int ks = trunk_pick_ksplit(c.Cin, c.KW, c.Cout, B, W4, 1);
     if (ks < 1) return false;
@@ -1159,9 +1197,9 @@ static bool trunk_fwd_ksplit(Exec& ex, const ConvSpec& c, const float* const* P,
     if (ex.dry) return true;
     TrunkArgs a{};
     a.a0 = P[c.wi[0]]; a.bias0 = P[c.bi[0]];
-    a.x = x; a.x_sc = (long long)B * W4; a.x_sb = W4;
+    a.x = x.p; a.x_sc = x.sc; a.x_sb = x.sb;
     a.Cin = c.Cin; a.KW = c.KW; a.K = c.Cin * c.KW; a.M = c.Cout; a.Mtot = c.Cout; a.B = B; a.T4 = W4; a.N = B * W4;
-    a.conv_out = conv_out; a.c_sc = (long long)B * W4; a.c_sb = W4; a.accumulate = 0; a.mode = TRUNK_PLAIN;
+    a.conv_out = conv_out.p; a.c_sc = conv_out.sc; a.c_sb = conv_out.sb; a.accumulate = 0; a.mode = TRUNK_PLAIN;
     a.slabs = ex.slabs; a.slab_stride = tot;
     ex.fail(mcvc_trunk_launch(a, ks, ex.s));
     return true;
@@ -1189,16 +1227,17 @@ static int fuse_wino_norm()
     return en;
 }
 
-static void norm_fwd(Exec& ex, float* x, long long x_sn, long long x_sc, long long x_total, int nslab, const NormP& np, float* stats,
-                     float* y, long long y_sn, long long y_sc, int y_sh, const float* res, int N, int C, int H, int W, int act)
+// x: the conv output (2C channels in front of a GLU) with its `nslab - 1` K-split slabs; y gives the shape, and its layout the store
+// (phase-split padded when y feeds an implicit-GEMM layer)
+static void norm_fwd(Exec& ex, Tensor x, int nslab, const NormP& np, float* stats, Tensor y, const float* res, int act)
 {
-    if (ex.dry) { ex.y_xs_pw = 0; return; }
+    if (ex.dry) return;
     NormArgs a{};
-    a.x = x; a.x_slabs = ex.slabs; a.x_sn = x_sn; a.x_sc = x_sc; a.slab_stride = x_total; a.nslab = nslab;
+    a.x = x.p; a.x_slabs = ex.slabs; a.x_sn = x.sb; a.x_sc = x.sc; a.slab_stride = x.dense(); a.nslab = nslab;
     a.gamma[0] = np.g[0]; a.gamma[1] = np.g[1]; a.beta[0] = np.b[0]; a.beta[1] = np.b[1];
-    a.stats = stats; a.y = y; a.res = res; a.y_sn = y_sn; a.y_sc = y_sc; a.y_sh = y_sh;
-    a.N = N; a.C = C; a.H = H; a.W = W; a.act = act; a.eps = kInEps;
-    if (ex.y_xs_pw) { a.y_xs = 1; a.xs_pw = ex.y_xs_pw; a.xs_plane = ex.y_xs_plane; ex.y_xs_pw = 0; }
+    a.stats = stats; a.y = y.p; a.res = res; a.y_sn = y.sb; a.y_sc = y.sc; a.y_sh = y.sh;
+    a.N = y.N; a.C = y.C; a.H = y.H; a.W = y.W; a.act = act; a.eps = kInEps;
+    if (y.lay == L_PHASE_SPLIT) { a.y_xs = 1; a.xs_pw = mcvc_xs_pw(y.W); a.xs_plane = mcvc_xs_plane(y.H, y.W); }
     if (ex.pend_fam) {
         const WinoFam& f = *ex.pend_fam;
         ex.pend_fam = nullptr;
@@ -1208,36 +1247,83 @@ static void norm_fwd(Exec& ex, float* x, long long x_sn, long long x_sc, long lo
     ex.fail(mcvc_norm_fwd_launch(a, ex.s));
 }
 
-static void norm_bwd(Exec& ex, const float* x, long long x_sn, long long x_sc, const NormP& np, const float* stats,
-                     float* dy, long long y_sn, long long y_sc, int y_sh, long long dy_total, int nslab,
-                     float* dx, long long dx_sn, long long dx_sc, int dx_sh, int unshuffle, int N, int C, int H, int W, int act)
+// dy: the gradient of the norm's output with its slabs, it gives the shape; dx: the conv output's gradient -- un-shuffled into conv-output
+// coordinates behind a PixelShuffle (`unshuffle`), in the padded dY layout when an implicit data gradient reads it
+static void norm_bwd(Exec& ex, CTensor x, const NormP& np, const float* stats, Tensor dy, int nslab, Tensor dx, int unshuffle, int act)
 {
-    if (ex.dry) { ex.dx_pitch = 0; return; }
-    wait_readers(ex, dx);
+    if (ex.dry) return;
+    wait_readers(ex, dx.p);
     NormBwdArgs a{};
-    a.x = x; a.x_sn = x_sn; a.x_sc = x_sc;
+    a.x = x.p; a.x_sn = x.sb; a.x_sc = x.sc;
     a.gamma[0] = np.g[0]; a.gamma[1] = np.g[1]; a.beta[0] = np.b[0]; a.beta[1] = np.b[1];
-    a.stats = stats; a.dy = dy; a.dy_slabs = ex.slabs; a.y_sn = y_sn; a.y_sc = y_sc; a.y_sh = y_sh; a.slab_stride = dy_total; a.nslab = nslab;
-    a.dx = dx; a.dx_sn = dx_sn; a.dx_sc = dx_sc; a.dx_sh = dx_sh; a.unshuffle = unshuffle;
+    a.stats = stats; a.dy = dy.p; a.dy_slabs = ex.slabs; a.y_sn = dy.sb; a.y_sc = dy.sc; a.y_sh = dy.sh; a.slab_stride = dy.dense(); a.nslab = nslab;
+    a.dx = dx.p; a.dx_sn = dx.sb; a.dx_sc = dx.sc; a.dx_sh = dx.sh; a.unshuffle = unshuffle;
     a.dgamma[0] = np.dg[0]; a.dgamma[1] = np.dg[1]; a.dbeta[0] = np.db[0]; a.dbeta[1] = np.db[1];
-    a.N = N; a.C = C; a.H = H; a.W = W; a.act = act;
-    a.dx_pitch = ex.dx_pitch; ex.dx_pitch = 0;
+    a.N = dy.N; a.C = dy.C; a.H = dy.H; a.W = dy.W; a.act = act;
+    a.dx_pitch = dx.lay == L_PADDED_DY ? dx.sh : 0;
     ex.fail(mcvc_norm_bwd_launch(a, ex.s));
 }
 
-static void act_fwd(Exec& ex, float* x, long long x_total, int nslab, float* y, int N, int C, int P, int act)
+// dense tensors; y gives the shape (x has 2C channels in front of a GLU)
+static void act_fwd(Exec& ex, Tensor x, int nslab, Tensor y, int act)
 {
     if (ex.dry) return;
-    ActArgs a{}; a.x = x; a.x_slabs = ex.slabs; a.slab_stride = x_total; a.nslab = nslab; a.y = y; a.N = N; a.C = C; a.P = P; a.act = act;
+    ActArgs a{}; a.x = x.p; a.x_slabs = ex.slabs; a.slab_stride = x.dense(); a.nslab = nslab; a.y = y.p; a.N = y.N; a.C = y.C; a.P = y.P(); a.act = act;
     ex.fail(mcvc_act_fwd_launch(a, ex.s));
 }
+// the K-split slabs of t added into it, in place
+static void sum_slabs(Exec& ex, Tensor t, int nslab)
+{
+    if (nslab > 1) act_fwd(ex, t, nslab, t.at(nullptr), ACT_NONE);
+}
 
-static void act_bwd(Exec& ex, const float* x, float* dy, long long dy_total, int nslab, float* dx, int N, int C, int P, int act)
+static void act_bwd(Exec& ex, CTensor x, Tensor dy, int nslab, Tensor dx, int act)
 {
     if (ex.dry) return;
-    wait_readers(ex, dx);
-    ActBwdArgs a{}; a.x = x; a.dy = dy; a.dy_slabs = ex.slabs; a.slab_stride = dy_total; a.nslab = nslab; a.dx = dx; a.N = N; a.C = C; a.P = P; a.act = act;
+    wait_readers(ex, dx.p);
+    ActBwdArgs a{}; a.x = x.p; a.dy = dy.p; a.dy_slabs = ex.slabs; a.slab_stride = dy.dense(); a.nslab = nslab; a.dx = dx.p; a.N = dy.N; a.C = dy.C; a.P = dy.P(); a.act = act;
     ex.fail(mcvc_act_bwd_launch(a, ex.s));
+}
+
+// ---- stash: one table per network ---------------------------------------------------------------------------------------------------------
+// SK_BATCH: dense, batch-major.  SK_TRUNK: the 1-D trunk's [C][stash_B][W].  SK_STATS: 2 floats per channel and sample.  SK_SPLIT: the input
+// of a 3x3 stride-2 layer -- phase-split padded when the pass runs those layers as implicit GEMMs, dense otherwise; sized for the larger form.
+enum StashKind { SK_BATCH, SK_TRUNK, SK_STATS, SK_SPLIT };
+struct StashRow { int C, H, W; StashKind kind; };
+constexpr int kMaxStashRows = 64;
+struct Stash {
+    int n;
+    long long off[kMaxStashRows], floats[kMaxStashRows], win[kMaxStashRows], total;      // win: offset of the pass's first sample
+    Tensor t[kMaxStashRows];                               // as the pass addresses them: from its first sample on
+    const Tensor& operator[](int i) const { return t[i]; }
+};
+// Rows laid out back to back (each rounded up to 4 floats) for stash_B samples; the tensors are those of a pass over B samples from sample b0
+// on: a window moves every tensor by b0 x its sample stride -- a sample's floats when batch-major, W when the batch sits inside the channel.
+static Stash stash_layout(const StashRow* rows, int n, float* base, int B, int stash_B, int b0, bool split)
+{
+    Stash s{};
+    s.n = n;
+    for (int i = 0; i < n; ++i) {
+        const StashRow& r = rows[i];
+        long long per = (long long)r.C * r.H * r.W;       // floats per sample
+        Tensor t{};
+        switch (r.kind) {
+        case SK_BATCH: t = nchw(base, B, r.C, r.H, r.W); break;
+        case SK_TRUNK: t = trunk_rows(base, B, r.C, r.W, (long long)stash_B * r.W); break;
+        case SK_STATS: t = nchw(base, B, r.C, 1, 2); per = 2LL * r.C; break;
+        case SK_SPLIT: {
+            const long long xs = (r.H & 1) || (r.W & 1) ? 0 : mcvc_xs_floats(r.C, r.H, r.W);
+            t = split ? phase_split(base, B, r.C, r.H, r.W) : nchw(base, B, r.C, r.H, r.W);
+            if (xs > per) per = xs;
+        } break;
+        }
+        s.off[i] = s.total; s.floats[i] = stash_B * per;
+        s.win[i] = s.total + b0 * t.sb;
+        t.p += s.win[i];
+        s.t[i] = t;
+        s.total += (s.floats[i] + 3) & ~3LL;
+    }
+    return s;
 }
 
 // =================================================================================================
@@ -1303,37 +1389,51 @@ static GenDims gen_dims(int B, int T)
     return d;
 }
 
-struct GenStash {
-    long long xin, c1, y1, c2, s2, y2, c3, s3, y3, c4, s4, y4;
-    struct { long long ca, sa, ya, cb, sb, y; } r[6];
-    long long c6, s6, y6, c7, s7, y7, c8, s8, y8, total;
-};
-static GenStash gen_stash(const GenDims& d)
+// What the forward pass leaves for the backward pass, one row per tensor in stash order: c* conv outputs (a norm's input, value | gate
+// channels in front of a GLU), s* the norm's statistics, y* the layer outputs.  Offsets, window shifts and the walks' tensors all come
+// from here (stash_layout).
+enum { WT, WW2, WW4, WWU1, WWU2 };                         // which of GenDims' widths a row has
+enum GenStashId { GS_XIN, GS_C1, GS_Y1, GS_C2, GS_S2, GS_Y2, GS_C3, GS_S3, GS_Y3, GS_C4, GS_S4, GS_Y4,
+                  GS_RES,                                  // six residual blocks of six rows: GS_RES + 6 * i + R_*
+                  GS_C6 = GS_RES + 36, GS_S6, GS_Y6, GS_C7, GS_S7, GS_Y7, GS_C8, GS_S8, GS_Y8, GS_ROWS };
+enum { R_CA, R_SA, R_YA, R_CB, R_SB, R_Y };
+struct GenStashRow { int C, H, width; StashKind kind; };
+static const GenStashRow kGenStashHead[] = {
+    {2, 80, WT, SK_BATCH},                                                                           // stack(x * mask, mask)
+    {256, 80, WT, SK_BATCH}, {128, 80, WT, SK_BATCH},                                                // conv1 | GLU
+    {512, 40, WW2, SK_BATCH}, {512, 1, 0, SK_STATS}, {256, 40, WW2, SK_BATCH},                       // downSample1
+    {512, 20, WW4, SK_BATCH}, {512, 1, 0, SK_STATS}, {5120, 1, WW4, SK_TRUNK},                       // downSample2, stored [c*20+h][b][w]
+    {256, 1, WW4, SK_TRUNK}, {256, 1, 0, SK_STATS}, {256, 1, WW4, SK_TRUNK}};                        // conv2dto1d
+static const GenStashRow kGenStashBlock[] = {
+    {1024, 1, WW4, SK_TRUNK}, {1024, 1, 0, SK_STATS}, {512, 1, WW4, SK_TRUNK},                       // value | gate convs, GLU
+    {256, 1, WW4, SK_TRUNK}, {256, 1, 0, SK_STATS}, {256, 1, WW4, SK_TRUNK}};                        // out conv + skip
+static const GenStashRow kGenStashTail[] = {
+    {5120, 1, WW4, SK_TRUNK}, {5120, 1, 0, SK_STATS}, {256, 20, WW4, SK_BATCH},                      // conv1dto2d, stored NCHW
+    {256, 40, WWU1, SK_BATCH}, {256, 1, 0, SK_STATS}, {256, 40, WWU1, SK_BATCH},                     // upSample1 (behind its PixelShuffle)
+    {128, 80, WWU2, SK_BATCH}, {128, 1, 0, SK_STATS}, {128, 80, WWU2, SK_BATCH}};                    // upSample2
+// the generator's stash written by a pass over stash_B samples of d.T frames, as a pass over d.B samples from sample b0 on addresses it
+static Stash gen_stash(float* base, const GenDims& d, int stash_B, int b0 = 0)
 {
-    GenStash s{};
-    long long cur = 0;
-    auto take = [&](long long n) { const long long o = cur; cur += (n + 3) & ~3LL; return o; };
-    const long long B = d.B;
-    s.xin = take(B * 2 * 80 * d.T);
-    s.c1 = take(B * 256 * 80 * d.T);   s.y1 = take(B * 128 * 80 * d.T);
-    s.c2 = take(B * 512 * 40 * d.W2);  s.s2 = take(B * 512 * 2);  s.y2 = take(B * 256 * 40 * d.W2);
-    s.c3 = take(B * 512 * 20 * d.W4);  s.s3 = take(B * 512 * 2);  s.y3 = take(B * 5120 * d.W4);
-    s.c4 = take(B * 256 * d.W4);       s.s4 = take(B * 256 * 2);  s.y4 = take(B * 256 * d.W4);
-    for (int i = 0; i < 6; ++i) {
-        s.r[i].ca = take(B * 1024 * d.W4); s.r[i].sa = take(B * 1024 * 2); s.r[i].ya = take(B * 512 * d.W4);
-        s.r[i].cb = take(B * 256 * d.W4);  s.r[i].sb = take(B * 256 * 2);  s.r[i].y = take(B * 256 * d.W4);
-    }
-    s.c6 = take(B * 5120 * d.W4);      s.s6 = take(B * 5120 * 2); s.y6 = take(B * 5120 * d.W4);
-    s.c7 = take(B * 256 * 40 * d.Wu1); s.s7 = take(B * 256 * 2);  s.y7 = take(B * 256 * 40 * d.Wu1);
-    s.c8 = take(B * 128 * 80 * d.Wu2); s.s8 = take(B * 128 * 2);  s.y8 = take(B * 128 * 80 * d.Wu2);
-    s.total = cur;
-    return s;
+    const int widths[] = {d.T, d.W2, d.W4, d.Wu1, d.Wu2};
+    StashRow rows[GS_ROWS];
+    int n = 0;
+    auto add = [&](const GenStashRow* r, int k) { for (; k > 0; --k, ++r) rows[n++] = StashRow{r->C, r->H, widths[r->width], r->kind}; };
+    add(kGenStashHead, GS_RES);
+    for (int i = 0; i < 6; ++i) add(kGenStashBlock, 6);
+    add(kGenStashTail, GS_ROWS - GS_C6);
+    return stash_layout(rows, GS_ROWS, base, d.B, stash_B, b0, false);
 }
 
-struct GenScratch { long long ga, gb, gb2, dh, dt1, dt1b, dt2, dt3, dt3b, dtx1, dtx3, wv, wm, wino_floats, wv2, wm2, wu, wu_floats, sync, slabs; };
+struct GenScratch {
+    long long ga, gb, gb2, dh, dt1, dt1b, dt2, dt3, dt3b, dtx1, dtx3, wv, wm, wino_floats, wv2, wm2, wu, wu_floats, sync, slabs;
+    int B, W4;
+    // a gradient buffer of the 1-D trunk: [C][B][W4], the pass's own batch inside
+    Tensor trunk(float* sc, long long off, int C) const { return trunk_rows(sc + off, B, C, W4, (long long)B * W4); }
+};
 static GenScratch gen_scratch(const GenDims& d)
 {
     GenScratch s{};
+    s.B = d.B; s.W4 = d.W4;
     long long cur = 0;
     auto take = [&](long long n) { const long long o = cur; cur += (n + 3) & ~3LL; return o; };
     // first, so that its place does not depend on the batch size: callers share one scratch buffer between passes of different batch
@@ -1365,101 +1465,77 @@ static void gen_forward_impl(Exec& ex, const float* const* P, const float* packe
 {
     ex.params = P;
     const GenNet& g = gen_net();
-    const GenStash o = gen_stash(d);
-    const int B = d.B, T = d.T, W2 = d.W2, W4 = d.W4, Wu1 = d.Wu1, Wu2 = d.Wu2;
-    const long long BT4 = (long long)B * W4;
+    const Stash o = gen_stash(st, d, d.B);
+    auto res = [&](int i, int k) -> const Tensor& { return o[GS_RES + 6 * i + k]; };
+    const int B = d.B, T = d.T;
     int ns = 1;
     // ---- model.py:241-242  stack(x*mask, mask) -> gated 5x15 conv (value|gate in one launch)
-    if (!ex.dry) ex.fail(mcvc_prep_input_launch(x, mask, st + o.xin, B, 80 * T, ex.s));
-    conv_fwd(ex, g.conv1, packed, B, 80, T, CView{st + o.xin, 2LL * 80 * T, 80LL * T, T}, View{st + o.c1, 256LL * 80 * T, 80LL * T, T},
-             (long long)B * 256 * 80 * T, 0, 1, &ns);
-    act_fwd(ex, st + o.c1, (long long)B * 256 * 80 * T, ns, st + o.y1, B, 128, 80 * T, ACT_GLU);
+    if (!ex.dry) ex.fail(mcvc_prep_input_launch(x, mask, o[GS_XIN].p, B, 80 * T, ex.s));
+    conv_fwd(ex, g.conv1, packed, o[GS_XIN], o[GS_C1], 0, 1, &ns);
+    act_fwd(ex, o[GS_C1], ns, o[GS_Y1], ACT_GLU);
+    // a 2-D layer: conv (c = its output in the stash; PixelShuffle fused into the store) -> IN -> activation; the norm may absorb a Winograd output transform
+    auto conv_norm = [&](const ConvSpec& cs, const Tensor& xin, int c, int shuffle, const NormP& np, const Tensor& y, int act) {
+        ex.fuse_next = fuse_wino_norm();
+        conv_fwd(ex, cs, packed, xin, o[c], shuffle, 1, &ns);
+        ex.fuse_next = 0;
+        norm_fwd(ex, o[c], ns, np, o[c + 1].p, y, nullptr, act);
+    };
     // ---- :245  downSample1 (5x5 s2, IN, GLU)
-    ex.fuse_next = fuse_wino_norm();
-    conv_fwd(ex, g.ds1, packed, B, 80, T, CView{st + o.y1, 128LL * 80 * T, 80LL * T, T}, View{st + o.c2, 512LL * 40 * W2, 40LL * W2, W2},
-             (long long)B * 512 * 40 * W2, 0, 1, &ns);
-    ex.fuse_next = 0;
-    norm_fwd(ex, st + o.c2, 512LL * 40 * W2, 40LL * W2, (long long)B * 512 * 40 * W2, ns, normp(P, nullptr, 6, 7, 10, 11), st + o.s2,
-             st + o.y2, 256LL * 40 * W2, 40LL * W2, W2, nullptr, B, 256, 40, W2, ACT_GLU);
+    conv_norm(g.ds1, o[GS_Y1], GS_C2, 0, normp(P, nullptr, 6, 7, 10, 11), o[GS_Y2], ACT_GLU);
     // ---- :246  downSample2; output written straight in trunk layout [c*20+h][b][w]  (:249-251)
-    ex.fuse_next = fuse_wino_norm();
-    conv_fwd(ex, g.ds2, packed, B, 40, W2, CView{st + o.y2, 256LL * 40 * W2, 40LL * W2, W2}, View{st + o.c3, 512LL * 20 * W4, 20LL * W4, W4},
-             (long long)B * 512 * 20 * W4, 0, 1, &ns);
-    ex.fuse_next = 0;
-    norm_fwd(ex, st + o.c3, 512LL * 20 * W4, 20LL * W4, (long long)B * 512 * 20 * W4, ns, normp(P, nullptr, 14, 15, 18, 19), st + o.s3,
-             st + o.y3, W4, 20LL * BT4, (int)BT4, nullptr, B, 256, 20, W4, ACT_GLU);
+    conv_norm(g.ds2, o[GS_Y2], GS_C3, 0, normp(P, nullptr, 14, 15, 18, 19), o[GS_Y3].rows20(), ACT_GLU);
     // ---- :254-255  1x1 5120->256 + IN ; image = [5120][B rows][W4]
-    if (trunk_fwd_ksplit(ex, g.c2d1d, P, st + o.y3, st + o.c4, B, W4, &ns)) {}
-    else conv_fwd(ex, g.c2d1d, packed, 1, B, W4, CView{st + o.y3, 0, BT4, W4}, View{st + o.c4, 0, BT4, W4}, 256 * BT4, 0, 1, &ns);
-    norm_fwd(ex, st + o.c4, W4, BT4, 256 * BT4, ns, normp(P, nullptr, 22, 23), st + o.s4, st + o.y4, W4, BT4, W4, nullptr, B, 256, 1, W4, ACT_NONE);
+    if (trunk_fwd_ksplit(ex, g.c2d1d, P, o[GS_Y3], o[GS_C4], &ns)) {}
+    else conv_fwd(ex, g.c2d1d, packed, o[GS_Y3].image(), o[GS_C4].image(), 0, 1, &ns);
+    norm_fwd(ex, o[GS_C4], ns, normp(P, nullptr, 22, 23), o[GS_S4].p, o[GS_Y4], nullptr, ACT_NONE);
     // ---- :258-271  six residual GLU blocks + 1x1 256->5120 + IN (written as NCHW [B][256][20][W4], 5120 = c*20 + h)
-    const float* h = st + o.y4;
-    if (trunk_net_enabled() && trunk_enabled() && ex.sync && mcvc_trunk_net_applies(B, W4)) {
-        // small batch: the 12 dependent residual layers in ONE persistent launch (trunk.h)
-        if (!ex.dry) {
-            TrunkFwdNetArgs na{};
-            int l = 0;
-            auto fill = [&](const ConvSpec& c, int g0, int be0, int g1, int be1, const float* x, float* cvo, float* stats, float* y,
-                            long long y_sn, long long y_sc, const float* res, int rows) {
-                TrunkLayerDesc& d = na.L[l++];
-                d.a0 = P[c.wi[0]]; d.bias0 = P[c.bi[0]]; d.gamma0 = P[g0]; d.beta0 = P[be0];
-                if (c.nbr == 2) { d.a1 = P[c.wi[1]]; d.bias1 = P[c.bi[1]]; d.gamma1 = P[g1]; d.beta1 = P[be1]; }
-                d.x = x; d.conv_out = cvo; d.stats = stats; d.y = y; d.y_sn = y_sn; d.y_sc = y_sc; d.res = res;
-                d.Cin = c.Cin; d.KW = c.KW; d.M = c.Cout; d.mode = (c.nbr == 2) ? TRUNK_IN_GLU : TRUNK_IN; d.rows = rows;
-            };
-            for (int i = 0; i < 6; ++i) {
-                const int b = 24 + 12 * i;
-                fill(g.res_vg[i], b + 2, b + 3, b + 6, b + 7, h, st + o.r[i].ca, st + o.r[i].sa, st + o.r[i].ya, W4, BT4, nullptr, 8);
-                fill(g.res_out[i], b + 10, b + 11, -1, -1, st + o.r[i].ya, st + o.r[i].cb, st + o.r[i].sb, st + o.r[i].y, W4, BT4, h, 4);
-                h = st + o.r[i].y;
-            }
-            na.nlayers = l; na.B = B; na.T4 = W4; na.eps = kInEps; na.sync = ex.sync;
-            ex.fail(mcvc_trunk_fwd_net_launch(na, ex.s));
-        } else {
-            h = st + o.r[5].y;
+    // a 1-D layer (stash rows c, c + 1: conv output, statistics): the fused kernel where it applies, else a conv over the image of B rows + the norm
+    auto layer1d = [&](const ConvSpec& cs, int g0, int be0, int g1, int be1, const Tensor& xin, int c, const Tensor& y, const float* skip, int act) {
+        if (trunk_fwd(ex, cs, P, g0, be0, g1, be1, xin, o[c], o[c + 1].p, y, skip)) return;
+        conv_fwd(ex, cs, packed, xin.image(), o[c].image(), 0, 1, &ns);
+        norm_fwd(ex, o[c], ns, normp(P, nullptr, g0, be0, g1, be1), o[c + 1].p, y, skip, act);
+    };
+    const Tensor* h = &o[GS_Y4];
+    const Tensor y6 = o[GS_Y6].rows_as_channels();
+    // small batch: the 12 dependent residual layers in ONE persistent launch (trunk.h)
+    const bool persistent = trunk_net_enabled() && trunk_enabled() && ex.sync && mcvc_trunk_net_applies(B, d.W4);
+    if (persistent && !ex.dry) {
+        TrunkFwdNetArgs na{};
+        int l = 0;
+        auto fill = [&](const ConvSpec& c, int g0, int be0, int g1, int be1, const Tensor& x, const Tensor* r, const float* skip, int rows) {
+            TrunkLayerDesc& d = na.L[l++];           // r: the layer's conv output, statistics and output rows of the stash
+            d.a0 = P[c.wi[0]]; d.bias0 = P[c.bi[0]]; d.gamma0 = P[g0]; d.beta0 = P[be0];
+            if (c.nbr == 2) { d.a1 = P[c.wi[1]]; d.bias1 = P[c.bi[1]]; d.gamma1 = P[g1]; d.beta1 = P[be1]; }
+            d.x = x.p; d.conv_out = r[0].p; d.stats = r[1].p; d.y = r[2].p; d.y_sn = r[2].sb; d.y_sc = r[2].sc; d.res = skip;
+            d.Cin = c.Cin; d.KW = c.KW; d.M = c.Cout; d.mode = (c.nbr == 2) ? TRUNK_IN_GLU : TRUNK_IN; d.rows = rows;
+        };
+        for (int i = 0; i < 6; ++i) {
+            const int b = 24 + 12 * i;
+            fill(g.res_vg[i], b + 2, b + 3, b + 6, b + 7, *h, &res(i, R_CA), nullptr, 8);
+            fill(g.res_out[i], b + 10, b + 11, -1, -1, res(i, R_YA), &res(i, R_CB), h->p, 4);
+            h = &res(i, R_Y);
         }
-        // 1x1 256 -> 5120 + IN: 320 independent row tiles -- its own (wide) launch
-        if (!trunk_fwd(ex, g.c1d2d, P, 98, 99, -1, -1, h, st + o.c6, st + o.s6, st + o.y6, 5120LL * W4, W4, nullptr, B, W4)) ex.fail(MCVC_ERR_INVALID);
-    } else {
-    for (int i = 0; i < 6; ++i) {
+        na.nlayers = l; na.B = B; na.T4 = d.W4; na.eps = kInEps; na.sync = ex.sync;
+        ex.fail(mcvc_trunk_fwd_net_launch(na, ex.s));
+    }
+    for (int i = 0; i < 6 && !persistent; ++i) {
         const int b = 24 + 12 * i;
-        if (!trunk_fwd(ex, g.res_vg[i], P, b + 2, b + 3, b + 6, b + 7, h, st + o.r[i].ca, st + o.r[i].sa, st + o.r[i].ya, W4, BT4, nullptr, B, W4)) {
-            conv_fwd(ex, g.res_vg[i], packed, 1, B, W4, CView{h, 0, BT4, W4}, View{st + o.r[i].ca, 0, BT4, W4}, 1024 * BT4, 0, 1, &ns);
-            norm_fwd(ex, st + o.r[i].ca, W4, BT4, 1024 * BT4, ns, normp(P, nullptr, b + 2, b + 3, b + 6, b + 7), st + o.r[i].sa,
-                     st + o.r[i].ya, W4, BT4, W4, nullptr, B, 512, 1, W4, ACT_GLU);
-        }
-        if (!trunk_fwd(ex, g.res_out[i], P, b + 10, b + 11, -1, -1, st + o.r[i].ya, st + o.r[i].cb, st + o.r[i].sb, st + o.r[i].y, W4, BT4, h, B, W4)) {
-            conv_fwd(ex, g.res_out[i], packed, 1, B, W4, CView{st + o.r[i].ya, 0, BT4, W4}, View{st + o.r[i].cb, 0, BT4, W4}, 256 * BT4, 0, 1, &ns);
-            norm_fwd(ex, st + o.r[i].cb, W4, BT4, 256 * BT4, ns, normp(P, nullptr, b + 10, b + 11), st + o.r[i].sb,
-                     st + o.r[i].y, W4, BT4, W4, h, B, 256, 1, W4, ACT_NONE);
-        }
-        h = st + o.r[i].y;
+        layer1d(g.res_vg[i], b + 2, b + 3, b + 6, b + 7, *h, GS_RES + 6 * i + R_CA, res(i, R_YA), nullptr, ACT_GLU);
+        layer1d(g.res_out[i], b + 10, b + 11, -1, -1, res(i, R_YA), GS_RES + 6 * i + R_CB, res(i, R_Y), h->p, ACT_NONE);
+        h = &res(i, R_Y);
     }
-    // ---- :266-271  1x1 256->5120 + IN, written as NCHW [B][256][20][W4] (5120 = c*20 + h)
-    if (!trunk_fwd(ex, g.c1d2d, P, 98, 99, -1, -1, h, st + o.c6, st + o.s6, st + o.y6, 5120LL * W4, W4, nullptr, B, W4)) {
-        conv_fwd(ex, g.c1d2d, packed, 1, B, W4, CView{h, 0, BT4, W4}, View{st + o.c6, 0, BT4, W4}, 5120 * BT4, 0, 1, &ns);
-        norm_fwd(ex, st + o.c6, W4, BT4, 5120 * BT4, ns, normp(P, nullptr, 98, 99), st + o.s6, st + o.y6, 5120LL * W4, W4, W4, nullptr,
-                 B, 5120, 1, W4, ACT_NONE);
-    }
-    }
+    h = &res(5, R_Y);
+    // 1x1 256 -> 5120 + IN: 320 independent row tiles -- its own (wide) launch behind the persistent one, which needs the fused kernel
+    if (!persistent) layer1d(g.c1d2d, 98, 99, -1, -1, *h, GS_C6, y6, nullptr, ACT_NONE);
+    else if (!trunk_fwd(ex, g.c1d2d, P, 98, 99, -1, -1, *h, o[GS_C6], o[GS_S6].p, y6, nullptr)) ex.fail(MCVC_ERR_INVALID);
     // ---- :274  upSample1: conv 5x5 -> PixelShuffle(2) (fused into the store) -> IN -> x*sigmoid(x)
-    ex.fuse_next = fuse_wino_norm();
-    conv_fwd(ex, g.up1, packed, B, 20, W4, CView{st + o.y6, 256LL * 20 * W4, 20LL * W4, W4}, View{st + o.c7, 256LL * 40 * Wu1, 40LL * Wu1, Wu1},
-             (long long)B * 256 * 40 * Wu1, 1, 1, &ns);
-    ex.fuse_next = 0;
-    norm_fwd(ex, st + o.c7, 256LL * 40 * Wu1, 40LL * Wu1, (long long)B * 256 * 40 * Wu1, ns, normp(P, nullptr, 106, 107), st + o.s7,
-             st + o.y7, 256LL * 40 * Wu1, 40LL * Wu1, Wu1, nullptr, B, 256, 40, Wu1, ACT_SILU);
+    conv_norm(g.up1, o[GS_Y6], GS_C7, 1, normp(P, nullptr, 106, 107), o[GS_Y7], ACT_SILU);
     // ---- :275  upSample2
-    ex.fuse_next = fuse_wino_norm();
-    conv_fwd(ex, g.up2, packed, B, 40, Wu1, CView{st + o.y7, 256LL * 40 * Wu1, 40LL * Wu1, Wu1}, View{st + o.c8, 128LL * 80 * Wu2, 80LL * Wu2, Wu2},
-             (long long)B * 128 * 80 * Wu2, 1, 1, &ns);
-    ex.fuse_next = 0;
-    norm_fwd(ex, st + o.c8, 128LL * 80 * Wu2, 80LL * Wu2, (long long)B * 128 * 80 * Wu2, ns, normp(P, nullptr, 102, 103), st + o.s8,
-             st + o.y8, 128LL * 80 * Wu2, 80LL * Wu2, Wu2, nullptr, B, 128, 80, Wu2, ACT_SILU);
+    conv_norm(g.up2, o[GS_Y7], GS_C8, 1, normp(P, nullptr, 102, 103), o[GS_Y8], ACT_SILU);
     // ---- :278-279  last 5x15 conv to one channel
-    conv_fwd(ex, g.last, packed, B, 80, Wu2, CView{st + o.y8, 128LL * 80 * Wu2, 80LL * Wu2, Wu2}, View{out, 80LL * Wu2, 80LL * Wu2, Wu2},
-             (long long)B * 80 * Wu2, 0, 1, &ns);
-    if (ns > 1) act_fwd(ex, out, (long long)B * 80 * Wu2, ns, nullptr, B, 1, 80 * Wu2, ACT_NONE);
+    const Tensor yo = nchw(out, B, 1, 80, d.Wu2);
+    conv_fwd(ex, g.last, packed, o[GS_Y8], yo, 0, 1, &ns);
+    sum_slabs(ex, yo, ns);
 }
 
 // every gradient kernel launched so far (main stream: norm / bias gradients; aux stream: weight gradients) is ordered
@@ -1467,38 +1543,14 @@ static void gen_forward_impl(Exec& ex, const float* const* P, const float* packe
 static void record_milestone(Exec& ex, void* ev)
 {
     if (!ev || ex.dry) return;
-    hipStream_t on = ex.s;
-    if (ex.s2) {
-        hipEvent_t e = pool_event();
-        ex.fail(mcvc_event_record(e, ex.s));
-        ex.fail(mcvc_stream_wait(ex.s2, e));
-        on = ex.s2;
-    }
-    ex.fail(mcvc_event_record((hipEvent_t)ev, on));
-}
-
-// sample b0 of every stash tensor becomes sample 0: batch-major tensors move by b0 samples, the trunk-layout ones ([C][stash_B][W4]) by b0 rows
-static void shift_stash(GenStash& s, const GenDims& d, int b0)
-{
-    if (b0 <= 0) return;
-    const long long b = b0, T = d.T, W2 = d.W2, W4 = d.W4;
-    s.xin += b * 2 * 80 * T; s.c1 += b * 256 * 80 * T; s.y1 += b * 128 * 80 * T;
-    s.c2 += b * 512 * 40 * W2; s.s2 += b * 512 * 2; s.y2 += b * 256 * 40 * W2;
-    s.c3 += b * 512 * 20 * W4; s.s3 += b * 512 * 2; s.y3 += b * W4;
-    s.c4 += b * W4; s.s4 += b * 256 * 2; s.y4 += b * W4;
-    for (int i = 0; i < 6; ++i) {
-        s.r[i].ca += b * W4; s.r[i].sa += b * 1024 * 2; s.r[i].ya += b * W4;
-        s.r[i].cb += b * W4; s.r[i].sb += b * 256 * 2; s.r[i].y += b * W4;
-    }
-    s.c6 += b * W4; s.s6 += b * 5120 * 2; s.y6 += b * 5120 * W4;
-    s.c7 += b * 256 * 40 * d.Wu1; s.s7 += b * 256 * 2; s.y7 += b * 256 * 40 * d.Wu1;
-    s.c8 += b * 128 * 80 * d.Wu2; s.s8 += b * 128 * 2; s.y8 += b * 128 * 80 * d.Wu2;
+    ex.fail(mcvc_event_record((hipEvent_t)ev, fork_aux(ex)));
 }
 
 // `stash_B` > B: the stash was written by a forward pass over stash_B samples and this pass back-propagates through its samples
 // [stash_b0, stash_b0 + B) only (the trainer's merged forwards: train.py:203-210 of iteration t+1 batched with :259-273 of iteration t, which
-// need no gradient; and the identity sample's backward, which depends on nothing but its own forward, ahead of the others').  The 2-D
-// tensors of the stash are batch-major, so a window is a pointer offset; the 1-D trunk's are [C][stash_B][W4]: their channel pitch is SBT4.
+// need no gradient; and the identity sample's backward, which depends on nothing but its own forward, ahead of the others').  The stash
+// table hands out the window's tensors (gen_stash): the batch-major ones start b0 samples in, the 1-D trunk's b0 rows in with the stash's
+// channel pitch stash_B * W4; the gradients of the trunk (GenScratch::trunk) have the pass's own, B * W4.
 static void gen_backward_impl(Exec& ex, const float* const* P, const float* packed, float* const* G, const float* mask, const float* dout,
                               float* dx, int accumulate_dx, const float* stc, float* sc, const GenDims& d, void* const* milestones = nullptr,
                               int stash_B = 0, int stash_b0 = 0)
@@ -1506,13 +1558,11 @@ static void gen_backward_impl(Exec& ex, const float* const* P, const float* pack
     ex.params = P;
     const GenNet& g = gen_net();
     if (stash_B < d.B) stash_B = d.B;
-    GenStash o = gen_stash(gen_dims(stash_B, d.T));
-    shift_stash(o, d, stash_b0);
+    // (stash is read-only here; kernels take non-const for slab-reduce paths that are not used on it)
+    const Stash o = gen_stash(const_cast<float*>(stc), d, stash_B, stash_b0);
+    auto res = [&](int i, int k) -> const Tensor& { return o[GS_RES + 6 * i + k]; };
     const GenScratch q = gen_scratch(d);
-    float* st = const_cast<float*>(stc);     // stash is read-only here; kernels take non-const for slab-reduce paths that are not used on it
-    const int B = d.B, T = d.T, W2 = d.W2, W4 = d.W4, Wu1 = d.Wu1, Wu2 = d.Wu2;
-    const long long BT4 = (long long)B * W4;
-    const long long SBT4 = (long long)stash_B * W4;
+    const int B = d.B, T = d.T, W4 = d.W4, Wu1 = d.Wu1, Wu2 = d.Wu2;
     const int pxB = stash_B > B ? stash_B : 0;
     // (float4 paths of the trunk kernels need 16-byte aligned rows: a window that starts at an odd multiple of W4 < 4 floats would not be)
     if (stash_b0 > 0 && (((long long)stash_b0 * W4) & 3)) { ex.fail(MCVC_ERR_INVALID); return; }
@@ -1520,55 +1570,38 @@ static void gen_backward_impl(Exec& ex, const float* const* P, const float* pack
     // main stream already produces layer k-1's
     float* GA = sc + q.ga;
     float* GBs[2] = {sc + q.gb, sc + q.gb2};
-    float* DT1s[2] = {sc + q.dt1, sc + q.dt1b};
-    float* DT3s[2] = {sc + q.dt3, sc + q.dt3b};
+    const Tensor DT1s[2] = {q.trunk(sc, q.dt1, 1024), q.trunk(sc, q.dt1b, 1024)};
+    const Tensor DT3s[2] = {q.trunk(sc, q.dt3, 256), q.trunk(sc, q.dt3b, 256)};
+    const Tensor DTX1 = q.trunk(sc, q.dtx1, 6 * 1024), DTX3 = q.trunk(sc, q.dtx3, 6 * 256);      // (small batch: a sixth per residual block)
     int gbi = 0;
     auto nextGB = [&]() { gbi ^= 1; return GBs[gbi]; };
     float* GB = GBs[0];
-    float* DH = sc + q.dh; float* DT1 = DT1s[0]; float* DT2 = sc + q.dt2; float* DT3 = DT3s[0];
+    const Tensor DH = q.trunk(sc, q.dh, 256), DT2 = q.trunk(sc, q.dt2, 512);
     int ns = 1;
+    // one 2-D layer behind its norm: weight, bias and data gradient of conv c from dY (conv-output layout) and the stashed input x
+    auto conv_bwd = [&](const ConvSpec& c, CTensor x, CTensor dy, Tensor dx_) {
+        conv_wgrad(ex, c, G, x, dy);
+        conv_bias_grad(ex, c, G, dy);
+        conv_dgrad(ex, c, packed, dy, dx_, 0, 1, &ns);
+    };
     // ---- last conv (model.py:278)
-    {
-        CView dyv{dout, 80LL * Wu2, 80LL * Wu2, Wu2};
-        CView xv{st + o.y8, 128LL * 80 * Wu2, 80LL * Wu2, Wu2};
-        conv_wgrad(ex, g.last, G, B, 80, Wu2, xv, dyv);
-        conv_bias_grad(ex, g.last, G, B, dyv, 80 * Wu2);
-        conv_dgrad(ex, g.last, packed, B, 80, Wu2, dyv, View{GA, 128LL * 80 * Wu2, 80LL * Wu2, Wu2}, (long long)B * 128 * 80 * Wu2, 0, 1, &ns);
-    }
+    conv_bwd(g.last, o[GS_Y8], nchw(dout, B, 1, 80, Wu2), o[GS_Y8].at(GA));
     // ---- upSample2 (:275): IN+SiLU backward, un-shuffled into conv-output coordinates [B][512][40][Wu1]
     GB = nextGB();
-    norm_bwd(ex, st + o.c8, 128LL * 80 * Wu2, 80LL * Wu2, normp(P, G, 102, 103), st + o.s8, GA, 128LL * 80 * Wu2, 80LL * Wu2, Wu2,
-             (long long)B * 128 * 80 * Wu2, ns, GB, 512LL * 40 * Wu1, 40LL * Wu1, Wu1, 1, B, 128, 80, Wu2, ACT_SILU);
-    {
-        CView dyv{GB, 512LL * 40 * Wu1, 40LL * Wu1, Wu1};
-        CView xv{st + o.y7, 256LL * 40 * Wu1, 40LL * Wu1, Wu1};
-        conv_wgrad(ex, g.up2, G, B, 40, Wu1, xv, dyv);
-        conv_bias_grad(ex, g.up2, G, B, dyv, 40 * Wu1);
-        conv_dgrad(ex, g.up2, packed, B, 40, Wu1, dyv, View{GA, 256LL * 40 * Wu1, 40LL * Wu1, Wu1}, (long long)B * 256 * 40 * Wu1, 0, 1, &ns);
-    }
+    norm_bwd(ex, o[GS_C8], normp(P, G, 102, 103), o[GS_S8].p, o[GS_C8].at(GA), ns, nchw(GB, B, 512, 40, Wu1), 1, ACT_SILU);
+    conv_bwd(g.up2, o[GS_Y7], nchw(GB, B, 512, 40, Wu1), o[GS_Y7].at(GA));
     // ---- upSample1 (:274)
     GB = nextGB();
-    norm_bwd(ex, st + o.c7, 256LL * 40 * Wu1, 40LL * Wu1, normp(P, G, 106, 107), st + o.s7, GA, 256LL * 40 * Wu1, 40LL * Wu1, Wu1,
-             (long long)B * 256 * 40 * Wu1, ns, GB, 1024LL * 20 * W4, 20LL * W4, W4, 1, B, 256, 40, Wu1, ACT_SILU);
-    {
-        CView dyv{GB, 1024LL * 20 * W4, 20LL * W4, W4};
-        CView xv{st + o.y6, 256LL * 20 * W4, 20LL * W4, W4};
-        conv_wgrad(ex, g.up1, G, B, 20, W4, xv, dyv);
-        conv_bias_grad(ex, g.up1, G, B, dyv, 20 * W4);
-        conv_dgrad(ex, g.up1, packed, B, 20, W4, dyv, View{GA, 256LL * 20 * W4, 20LL * W4, W4}, (long long)B * 5120 * W4, 0, 1, &ns);
-    }
+    norm_bwd(ex, o[GS_C7], normp(P, G, 106, 107), o[GS_S7].p, o[GS_C7].at(GA), ns, nchw(GB, B, 1024, 20, W4), 1, ACT_SILU);
+    conv_bwd(g.up1, o[GS_Y6], nchw(GB, B, 1024, 20, W4), o[GS_Y6].at(GA));
     if (milestones) record_milestone(ex, milestones[0]);          // parameters [100,110) are done
     // ---- conv1dto2d + IN (:266-271): dy arrives NCHW, dx leaves in trunk layout
     GB = nextGB();
-    norm_bwd(ex, st + o.c6, W4, SBT4, normp(P, G, 98, 99), st + o.s6, GA, 5120LL * W4, W4, W4, 5120 * BT4, ns,
-             GB, W4, BT4, W4, 0, B, 5120, 1, W4, ACT_NONE);
-    {
-        const float* hin = st + o.r[5].y;
-        CView dyv{GB, 0, BT4, W4};
-        conv_wgrad(ex, g.c1d2d, G, 1, B, W4, CView{hin, 0, SBT4, W4}, dyv);
-        if (trunk_dgrad(ex, g.c1d2d, packed, GB, DH, 0, B, W4, &ns)) {}
-        else conv_dgrad(ex, g.c1d2d, packed, 1, B, W4, dyv, View{DH, 0, BT4, W4}, 256 * BT4, 0, 1, &ns);
-    }
+    const Tensor dy6 = q.trunk(GB, 0, 5120);
+    norm_bwd(ex, o[GS_C6], normp(P, G, 98, 99), o[GS_S6].p, o[GS_Y6].at(GA).rows_as_channels(), ns, dy6, 0, ACT_NONE);
+    conv_wgrad(ex, g.c1d2d, G, res(5, R_Y).image(), dy6.image());
+    if (trunk_dgrad(ex, g.c1d2d, packed, dy6, DH, 0, &ns)) {}
+    else conv_dgrad(ex, g.c1d2d, packed, dy6.image(), DH.image(), 0, 1, &ns);
     // ---- residual blocks (:258-263), last to first.  DH carries d(h) and is updated in place.
     // small batch: the InstanceNorm backward of each layer is recomputed inside the data-gradient launch that consumes it (one thread
     // per channel of the workgroup's K slice) -- 2 dependent launches per residual block instead of 4.  Needs an un-split upstream
@@ -1579,6 +1612,12 @@ static void gen_backward_impl(Exec& ex, const float* const* P, const float* pack
     int nwjobs = 0;
     const bool batch_w = batch_knob && mcvc_wgrad_smallk_batch_applies(B, W4) && (W4 <= 128);
     auto wstore = [&](const ConvSpec& c) { return (ex.store_grads && grad_store_covered(c)) ? 1 : 0; };      // (the batched launch's per-job flag)
+    // the weight gradients of block i, queued for the batched launch behind the chain: out conv, value conv, gate conv
+    auto queue_wgrads = [&](int i, const Tensor& hin, const Tensor& dt3, const Tensor& dt1) {
+        wjobs[nwjobs++] = SmallKJob{res(i, R_YA).p, dt3.p, G[g.res_out[i].wi[0]], 512, 256, pxB, wstore(g.res_out[i])};
+        wjobs[nwjobs++] = SmallKJob{hin.p, dt1.p, G[g.res_vg[i].wi[0]], 256, 512, pxB, wstore(g.res_vg[i])};
+        wjobs[nwjobs++] = SmallKJob{hin.p, dt1.channels(512, 512).p, G[g.res_vg[i].wi[1]], 256, 512, pxB, wstore(g.res_vg[i])};
+    };
     // Persistent backward (trunk.h): the 12 dependent data-gradient layers of the six blocks in ONE launch, when every layer would take the
     // fused path anyway, the gradient arriving from conv1dto2d is not split into slabs and the staged gradients fit the LDS
     static const int bwd_net_knob = mcvc_knob("MCVC_TRUNK_BWD_NET", 1);
@@ -1591,126 +1630,91 @@ static void gen_backward_impl(Exec& ex, const float* const* P, const float* pack
         int l = 0;
         for (int i = 5; i >= 0; --i) {
             const int b = 24 + 12 * i;
-            const float* hin = (i == 0) ? (st + o.y4) : (st + o.r[i - 1].y);
-            float* dt3 = sc + q.dtx3 + (long long)i * 256 * BT4;
-            float* dt1 = sc + q.dtx1 + (long long)i * 1024 * BT4;
+            const Tensor& hin = (i == 0) ? o[GS_Y4] : res(i - 1, R_Y);
+            const Tensor dt3 = DTX3.channels(i * 256, 256), dt1 = DTX1.channels(i * 1024, 1024);
             TrunkBwdLayerDesc& da = na.L[l++];           // conv1d_out_layer (512 -> 256) + its InstanceNorm: d(h_out) -> d(GLU output)
-            da.wt = packed + g.res_out[i].off[PF_TRUNK_T]; da.dy = DH; da.px = st + o.r[i].cb; da.stats = st + o.r[i].sb;
-            da.g0 = P[b + 10]; da.b0 = P[b + 11]; da.xout = dt3; da.pxB = pxB; da.dg0 = G[b + 10]; da.db0 = G[b + 11];
-            da.out = DT2; da.pre = 1; da.C = 256; da.M = 512; da.rows = 8;
+            da.wt = packed + g.res_out[i].off[PF_TRUNK_T]; da.dy = DH.p; da.px = res(i, R_CB).p; da.stats = res(i, R_SB).p;
+            da.g0 = P[b + 10]; da.b0 = P[b + 11]; da.xout = dt3.p; da.pxB = pxB; da.dg0 = G[b + 10]; da.db0 = G[b + 11];
+            da.out = DT2.p; da.pre = 1; da.C = 256; da.M = 512; da.rows = 8;
             da.flags = (i < 5 ? TBWD_DY_FRESH : 0) | ((i == 5 && ns > 1) ? TBWD_SLAB_DY : 0);            // (conv1dto2d's K-split slabs)
             TrunkBwdLayerDesc& db = na.L[l++];           // value | gate convs (256 -> 512 each) + norms + GLU: d(GLU output) -> d(h_in), added to the skip path
-            db.wt = packed + g.res_vg[i].off[PF_TRUNK_T]; db.dy = DT2; db.px = st + o.r[i].ca; db.stats = st + o.r[i].sa;
-            db.g0 = P[b + 2]; db.b0 = P[b + 3]; db.g1 = P[b + 6]; db.b1 = P[b + 7]; db.xout = dt1; db.pxB = pxB;
+            db.wt = packed + g.res_vg[i].off[PF_TRUNK_T]; db.dy = DT2.p; db.px = res(i, R_CA).p; db.stats = res(i, R_SA).p;
+            db.g0 = P[b + 2]; db.b0 = P[b + 3]; db.g1 = P[b + 6]; db.b1 = P[b + 7]; db.xout = dt1.p; db.pxB = pxB;
             db.dg0 = G[b + 2]; db.db0 = G[b + 3]; db.dg1 = G[b + 6]; db.db1 = G[b + 7];
-            db.out = DH; db.pre = 2; db.C = 512; db.M = 256; db.rows = 4;
+            db.out = DH.p; db.pre = 2; db.C = 512; db.M = 256; db.rows = 4;
             db.flags = TBWD_ACCUMULATE | TBWD_DY_FRESH | ((i == 5 && ns > 1) ? TBWD_SLAB_OUT : 0);
-            wjobs[nwjobs++] = SmallKJob{st + o.r[i].ya, dt3, G[g.res_out[i].wi[0]], 512, 256, pxB, wstore(g.res_out[i])};
-            wjobs[nwjobs++] = SmallKJob{hin, dt1, G[g.res_vg[i].wi[0]], 256, 512, pxB, wstore(g.res_vg[i])};
-            wjobs[nwjobs++] = SmallKJob{hin, dt1 + 512LL * BT4, G[g.res_vg[i].wi[1]], 256, 512, pxB, wstore(g.res_vg[i])};
+            queue_wgrads(i, hin, dt3, dt1);
         }
-        na.nlayers = l; na.B = B; na.T4 = W4; na.slabs = ex.slabs; na.slab_stride = 256 * BT4; na.nslab = ns; na.sync = ex.sync + MCVC_TRUNK_SYNC_WORDS; na.err = ex.sync + MCVC_TRUNK_SYNC_WORDS - 1;
-        for (int i = 0; i < 6; ++i) { wait_readers(ex, sc + q.dtx3 + (long long)i * 256 * BT4); wait_readers(ex, sc + q.dtx1 + (long long)i * 1024 * BT4); }
+        na.nlayers = l; na.B = B; na.T4 = W4; na.slabs = ex.slabs; na.slab_stride = DH.dense(); na.nslab = ns; na.sync = ex.sync + MCVC_TRUNK_SYNC_WORDS; na.err = ex.sync + MCVC_TRUNK_SYNC_WORDS - 1;
+        for (int i = 0; i < 6; ++i) { wait_readers(ex, DTX3.channels(i * 256, 256).p); wait_readers(ex, DTX1.channels(i * 1024, 1024).p); }
         ex.fail(mcvc_trunk_bwd_net_launch(na, ex.s));
         ns = 1;
     }
     for (int i = 5; i >= 0 && !bwd_net; --i) {
         const int b = 24 + 12 * i;
-        const float* hin = (i == 0) ? (st + o.y4) : (st + o.r[i - 1].y);
-        DT3 = DT3s[i & 1]; DT1 = DT1s[i & 1];
+        const Tensor& hin = (i == 0) ? o[GS_Y4] : res(i - 1, R_Y);
+        Tensor DT3 = DT3s[i & 1], DT1 = DT1s[i & 1];
         const bool fuse = fuse_knob && trunk_enabled() && ns == 1 && !ex.dry && G && g.res_out[i].off[PF_TRUNK_T] >= 0 && g.res_vg[i].off[PF_TRUNK_T] >= 0 &&
                           mcvc_trunk_applies(g.res_out[i].cout_tot, 3, g.res_out[i].Cin, B, W4, TRUNK_PLAIN, 1) &&
                           trunk_pick_ksplit(g.res_vg[i].cout_tot, 3, g.res_vg[i].Cin, B, W4, 0) >= 1;
         if (fuse) {
-            if (batch_w) { DT3 = sc + q.dtx3 + (long long)i * 256 * BT4; DT1 = sc + q.dtx1 + (long long)i * 1024 * BT4; }
-            TrunkPre pa{1, st + o.r[i].cb, st + o.r[i].sb, P[b + 10], P[b + 11], nullptr, nullptr, DT3, G[b + 10], G[b + 11], nullptr, nullptr, pxB};
-            trunk_dgrad(ex, g.res_out[i], packed, DH, DT2, 0, B, W4, nullptr, &pa);
-            TrunkPre pb{2, st + o.r[i].ca, st + o.r[i].sa, P[b + 2], P[b + 3], P[b + 6], P[b + 7], DT1, G[b + 2], G[b + 3], G[b + 6], G[b + 7], pxB};
+            if (batch_w) { DT3 = DTX3.channels(i * 256, 256); DT1 = DTX1.channels(i * 1024, 1024); }
+            TrunkPre pa{1, res(i, R_CB).p, res(i, R_SB).p, P[b + 10], P[b + 11], nullptr, nullptr, DT3.p, G[b + 10], G[b + 11], nullptr, nullptr, pxB};
+            trunk_dgrad(ex, g.res_out[i], packed, DH, DT2, 0, nullptr, &pa);
+            TrunkPre pb{2, res(i, R_CA).p, res(i, R_SA).p, P[b + 2], P[b + 3], P[b + 6], P[b + 7], DT1.p, G[b + 2], G[b + 3], G[b + 6], G[b + 7], pxB};
             ns = 1;
-            trunk_dgrad(ex, g.res_vg[i], packed, DT2, DH, 1, B, W4, &ns, &pb);
-            if (batch_w) {          // weight gradients of the block: queued for the batched launch behind the chain
-                wjobs[nwjobs++] = SmallKJob{st + o.r[i].ya, DT3, G[g.res_out[i].wi[0]], 512, 256, pxB, wstore(g.res_out[i])};
-                wjobs[nwjobs++] = SmallKJob{hin, DT1, G[g.res_vg[i].wi[0]], 256, 512, pxB, wstore(g.res_vg[i])};
-                wjobs[nwjobs++] = SmallKJob{hin, DT1 + 512LL * BT4, G[g.res_vg[i].wi[1]], 256, 512, pxB, wstore(g.res_vg[i])};
-            } else {
-                conv_wgrad(ex, g.res_out[i], G, 1, B, W4, CView{st + o.r[i].ya, 0, SBT4, W4}, CView{DT3, 0, BT4, W4});
-                conv_wgrad(ex, g.res_vg[i], G, 1, B, W4, CView{hin, 0, SBT4, W4}, CView{DT1, 0, BT4, W4});
+            trunk_dgrad(ex, g.res_vg[i], packed, DT2, DH, 1, &ns, &pb);
+            if (batch_w) queue_wgrads(i, hin, DT3, DT1);
+            else {
+                conv_wgrad(ex, g.res_out[i], G, res(i, R_YA).image(), DT3.image());
+                conv_wgrad(ex, g.res_vg[i], G, hin.image(), DT1.image());
             }
             continue;
         }
-        norm_bwd(ex, st + o.r[i].cb, W4, SBT4, normp(P, G, b + 10, b + 11), st + o.r[i].sb, DH, W4, BT4, W4, 256 * BT4, ns,
-                 DT3, W4, BT4, W4, 0, B, 256, 1, W4, ACT_NONE);
+        norm_bwd(ex, res(i, R_CB), normp(P, G, b + 10, b + 11), res(i, R_SB).p, DH, ns, DT3, 0, ACT_NONE);
         int ns2 = 1;
-        {
-            CView dyv{DT3, 0, BT4, W4};
-            conv_wgrad(ex, g.res_out[i], G, 1, B, W4, CView{st + o.r[i].ya, 0, SBT4, W4}, dyv);
-            if (!trunk_dgrad(ex, g.res_out[i], packed, DT3, DT2, 0, B, W4))
-                conv_dgrad(ex, g.res_out[i], packed, 1, B, W4, dyv, View{DT2, 0, BT4, W4}, 512 * BT4, 0, 1, &ns2);
-        }
-        norm_bwd(ex, st + o.r[i].ca, W4, SBT4, normp(P, G, b + 2, b + 3, b + 6, b + 7), st + o.r[i].sa, DT2, W4, BT4, W4, 512 * BT4, ns2,
-                 DT1, W4, BT4, W4, 0, B, 512, 1, W4, ACT_GLU);
-        {
-            CView dyv{DT1, 0, BT4, W4};
-            conv_wgrad(ex, g.res_vg[i], G, 1, B, W4, CView{hin, 0, SBT4, W4}, dyv);
-            ns = 1;          // (deterministic mode: DH is left alone and its K-split partials go to slabs the next norm_bwd sums)
-            if (!trunk_dgrad(ex, g.res_vg[i], packed, DT1, DH, 1 /*accumulate: skip path*/, B, W4, &ns))
-                conv_dgrad(ex, g.res_vg[i], packed, 1, B, W4, dyv, View{DH, 0, BT4, W4}, 256 * BT4, 1, 1, &ns);      // (a K split leaves its partials in slabs the next norm_bwd sums)
-        }
+        conv_wgrad(ex, g.res_out[i], G, res(i, R_YA).image(), DT3.image());
+        if (!trunk_dgrad(ex, g.res_out[i], packed, DT3, DT2, 0))
+            conv_dgrad(ex, g.res_out[i], packed, DT3.image(), DT2.image(), 0, 1, &ns2);
+        norm_bwd(ex, res(i, R_CA), normp(P, G, b + 2, b + 3, b + 6, b + 7), res(i, R_SA).p, DT2, ns2, DT1, 0, ACT_GLU);
+        conv_wgrad(ex, g.res_vg[i], G, hin.image(), DT1.image());
+        ns = 1;          // (deterministic mode: DH is left alone and its K-split partials go to slabs the next norm_bwd sums)
+        if (!trunk_dgrad(ex, g.res_vg[i], packed, DT1, DH, 1 /*accumulate: skip path*/, &ns))
+            conv_dgrad(ex, g.res_vg[i], packed, DT1.image(), DH.image(), 1, 1, &ns);      // (a K split leaves its partials in slabs the next norm_bwd sums)
     }
-    if (nwjobs > 0) {              // ONE launch for the residual layers' weight gradients, beside the rest of the backward chain
-        hipStream_t ws = ex.s;
-        if (ex.s2) {
-            hipEvent_t e = pool_event();
-            ex.fail(mcvc_event_record(e, ex.s));
-            ex.fail(mcvc_stream_wait(ex.s2, e));
-            ws = ex.s2;
-        }
-        ex.fail(mcvc_wgrad_smallk_batch_launch(wjobs, nwjobs, B, W4, ws));
-    }
+    // ONE launch for the residual layers' weight gradients, beside the rest of the backward chain
+    if (nwjobs > 0) ex.fail(mcvc_wgrad_smallk_batch_launch(wjobs, nwjobs, B, W4, fork_aux(ex)));
     if (milestones) record_milestone(ex, milestones[1]);          // parameters [24,100) are done
     // ---- conv2dto1d + IN (:254-255)
-    DT3 = DT3s[1];
-    norm_bwd(ex, st + o.c4, W4, SBT4, normp(P, G, 22, 23), st + o.s4, DH, W4, BT4, W4, 256 * BT4, ns, DT3, W4, BT4, W4, 0, B, 256, 1, W4, ACT_NONE);
-    {
-        CView dyv{DT3, 0, BT4, W4};
-        conv_wgrad(ex, g.c2d1d, G, 1, B, W4, CView{st + o.y3, 0, SBT4, W4}, dyv);
-        ns = 1;
-        if (!trunk_dgrad(ex, g.c2d1d, packed, DT3, GA, 0, B, W4))
-            conv_dgrad(ex, g.c2d1d, packed, 1, B, W4, dyv, View{GA, 0, BT4, W4}, 5120 * BT4, 0, 1, &ns);
-    }
+    const Tensor dy4 = DT3s[1], dy3 = q.trunk(GA, 0, 5120);
+    norm_bwd(ex, o[GS_C4], normp(P, G, 22, 23), o[GS_S4].p, DH, ns, dy4, 0, ACT_NONE);
+    conv_wgrad(ex, g.c2d1d, G, o[GS_Y3].image(), dy4.image());
+    ns = 1;
+    if (!trunk_dgrad(ex, g.c2d1d, packed, dy4, dy3, 0))
+        conv_dgrad(ex, g.c2d1d, packed, dy4.image(), dy3.image(), 0, 1, &ns);
     // ---- downSample2 (:246): dy is in trunk layout
     GB = nextGB();
-    norm_bwd(ex, st + o.c3, 512LL * 20 * W4, 20LL * W4, normp(P, G, 14, 15, 18, 19), st + o.s3, GA, W4, 20LL * BT4, (int)BT4, 5120 * BT4, ns,
-             GB, 512LL * 20 * W4, 20LL * W4, W4, 0, B, 256, 20, W4, ACT_GLU);
-    {
-        CView dyv{GB, 512LL * 20 * W4, 20LL * W4, W4};
-        conv_wgrad(ex, g.ds2, G, B, 40, W2, CView{st + o.y2, 256LL * 40 * W2, 40LL * W2, W2}, dyv);
-        conv_dgrad(ex, g.ds2, packed, B, 40, W2, dyv, View{GA, 256LL * 40 * W2, 40LL * W2, W2}, (long long)B * 256 * 40 * W2, 0, 1, &ns);
-    }
+    norm_bwd(ex, o[GS_C3], normp(P, G, 14, 15, 18, 19), o[GS_S3].p, dy3.rows20(), ns, o[GS_C3].at(GB), 0, ACT_GLU);
+    conv_wgrad(ex, g.ds2, G, o[GS_Y2], o[GS_C3].at(GB));
+    conv_dgrad(ex, g.ds2, packed, o[GS_C3].at(GB), o[GS_Y2].at(GA), 0, 1, &ns);
     if (milestones && ex.fine_ms) record_milestone(ex, milestones[2]);          // parameters [12,24) (downSample2, conv2dto1d) are done
     // ---- downSample1 (:245)
     GB = nextGB();
-    norm_bwd(ex, st + o.c2, 512LL * 40 * W2, 40LL * W2, normp(P, G, 6, 7, 10, 11), st + o.s2, GA, 256LL * 40 * W2, 40LL * W2, W2,
-             (long long)B * 256 * 40 * W2, ns, GB, 512LL * 40 * W2, 40LL * W2, W2, 0, B, 256, 40, W2, ACT_GLU);
-    {
-        CView dyv{GB, 512LL * 40 * W2, 40LL * W2, W2};
-        conv_wgrad(ex, g.ds1, G, B, 80, T, CView{st + o.y1, 128LL * 80 * T, 80LL * T, T}, dyv);
-        conv_dgrad(ex, g.ds1, packed, B, 80, T, dyv, View{GA, 128LL * 80 * T, 80LL * T, T}, (long long)B * 128 * 80 * T, 0, 1, &ns);
-    }
+    norm_bwd(ex, o[GS_C2], normp(P, G, 6, 7, 10, 11), o[GS_S2].p, o[GS_Y2].at(GA), ns, o[GS_C2].at(GB), 0, ACT_GLU);
+    conv_wgrad(ex, g.ds1, G, o[GS_Y1], o[GS_C2].at(GB));
+    conv_dgrad(ex, g.ds1, packed, o[GS_C2].at(GB), o[GS_Y1].at(GA), 0, 1, &ns);
     if (milestones && ex.fine_ms) record_milestone(ex, milestones[3]);          // parameters [4,12) (downSample1) are done
     // ---- conv1 gated GLU (:242)
     GB = nextGB();
-    act_bwd(ex, st + o.c1, GA, (long long)B * 128 * 80 * T, ns, GB, B, 128, 80 * T, ACT_GLU);
-    {
-        CView dyv{GB, 256LL * 80 * T, 80LL * T, T};
-        ex.br1_on_main = (dx == nullptr) ? 1 : 0;
-        conv_wgrad(ex, g.conv1, G, B, 80, T, CView{st + o.xin, 2LL * 80 * T, 80LL * T, T}, dyv);
-        ex.br1_on_main = 0;
-        conv_bias_grad(ex, g.conv1, G, B, dyv, 80 * T);
-        if (dx) {
-            conv_dgrad(ex, g.conv1, packed, B, 80, T, dyv, View{GA, 2LL * 80 * T, 80LL * T, T}, (long long)B * 2 * 80 * T, 0, 1, &ns);
-            if (!ex.dry) ex.fail(mcvc_mask_grad_launch(GA, ex.slabs, (long long)B * 2 * 80 * T, ns, mask, dx, B, 80 * T, 2, accumulate_dx, ex.s));
-        }
+    act_bwd(ex, o[GS_C1], o[GS_Y1].at(GA), ns, o[GS_C1].at(GB), ACT_GLU);
+    ex.br1_on_main = (dx == nullptr) ? 1 : 0;
+    conv_wgrad(ex, g.conv1, G, o[GS_XIN], o[GS_C1].at(GB));
+    ex.br1_on_main = 0;
+    conv_bias_grad(ex, g.conv1, G, o[GS_C1].at(GB));
+    if (dx) {
+        const Tensor dxin = o[GS_XIN].at(GA);
+        conv_dgrad(ex, g.conv1, packed, o[GS_C1].at(GB), dxin, 0, 1, &ns);
+        if (!ex.dry) ex.fail(mcvc_mask_grad_launch(GA, ex.slabs, dxin.dense(), ns, mask, dx, B, 80 * T, 2, accumulate_dx, ex.s));
     }
     if (ex.no_join) ex.readers.clear(); else join_aux(ex);
 }
@@ -1753,34 +1757,20 @@ static DiscDims disc_dims(int B, int T)
     for (int i = 1; i < 4; ++i) { const long long p = (long long)B * (128 << i) * mcvc_dyp_plane(d.H[i], d.W[i]); if (p > d.big) d.big = p; }
     return d;
 }
-static const int kDC[4] = {128, 256, 512, 1024};
 
-struct DiscStash { long long c0, y0, c[3], s[3], y[3], logit, total; };
-static DiscStash disc_stash(const DiscDims& d)
-{
-    DiscStash s{};
-    long long cur = 0;
-    auto take = [&](long long n) { const long long o = cur; cur += (n + 3) & ~3LL; return o; };
-    const long long B = d.B;
-    // (the inputs of the three stride-2 layers -- y0, y[0], y[1] -- may be stored in the phase-split padded layout of sgemm.h: the larger size)
-    auto xs_or_dense = [&](int C, int H, int W) { const long long xs = (H & 1) || (W & 1) ? 0 : mcvc_xs_floats(C, H, W); const long long dn = (long long)C * H * W; return B * (xs > dn ? xs : dn); };
-    s.c0 = take(B * 128 * 80 * d.T); s.y0 = take(xs_or_dense(128, 80, d.T));
-    for (int i = 0; i < 3; ++i) {
-        const long long n = B * kDC[i + 1] * d.H[i + 1] * d.W[i + 1];
-        s.c[i] = take(n); s.s[i] = take(B * kDC[i + 1] * 2); s.y[i] = take(i < 2 ? xs_or_dense(kDC[i + 1], d.H[i + 1], d.W[i + 1]) : n);
-    }
-    s.logit = take(B * d.H[3] * d.W[3]);
-    s.total = cur;
-    return s;
-}
-struct DiscScratch { long long ga, gb, gb2, slabs; };
-static DiscScratch disc_scratch(const DiscDims& d)
-{
-    DiscScratch s{};
-    s.ga = 0; s.gb = (d.big + 3) & ~3LL; s.gb2 = 2 * s.gb; s.slabs = 3 * s.gb;
-    return s;
-}
-
+// the discriminator's stash (see the generator's): level l = the l-th stride-2 layer; the inputs of those layers -- y0, y of levels 0 and 1 --
+// may be stored phase-split; the pass's input is copied behind the rest (the first layer's weight gradient reads it)
+enum DiscStashId { DS_C0, DS_Y0, DS_LEVEL,                  // three levels of three rows: DS_LEVEL + 3 * l + L_*
+                   DS_LOGIT = DS_LEVEL + 9, DS_XIN, DS_ROWS };
+enum { L_C, L_S, L_Y };
+struct DiscStashRow { int C, level; StashKind kind; };      // level: which of DiscDims' H[] x W[] planes
+static const DiscStashRow kDiscStash[DS_ROWS] = {
+    {128, 0, SK_BATCH}, {128, 0, SK_SPLIT},
+    {256, 1, SK_BATCH}, {256, 1, SK_STATS}, {256, 1, SK_SPLIT},
+    {512, 2, SK_BATCH}, {512, 2, SK_STATS}, {512, 2, SK_SPLIT},
+    {1024, 3, SK_BATCH}, {1024, 3, SK_STATS}, {1024, 3, SK_BATCH},
+    {1, 3, SK_BATCH}, {1, 0, SK_BATCH},
+};
 // the first (one input channel) and the output (one output channel) layer on their own kernels (fewout_kernels.hip) instead of the generic
 // conv + activation pairs
 static int disc_out_direct()
@@ -1798,48 +1788,51 @@ static bool disc_igemm(const DiscDims& d)
     return ok;
 }
 
+static Stash disc_stash(float* base, const DiscDims& d)
+{
+    StashRow rows[DS_ROWS];
+    for (int i = 0; i < DS_ROWS; ++i) { const DiscStashRow& r = kDiscStash[i]; rows[i] = StashRow{r.C, d.H[r.level], d.W[r.level], r.kind}; }
+    return stash_layout(rows, DS_ROWS, base, d.B, d.B, 0, disc_igemm(d));
+}
+struct DiscScratch { long long ga, gb, gb2, slabs; };
+static DiscScratch disc_scratch(const DiscDims& d)
+{
+    DiscScratch s{};
+    s.ga = 0; s.gb = (d.big + 3) & ~3LL; s.gb2 = 2 * s.gb; s.slabs = 3 * s.gb;
+    return s;
+}
+
 static void disc_forward_impl(Exec& ex, const float* const* P, const float* packed, const float* x, float* out, float* st, const DiscDims& d)
 {
     ex.params = P;
     const DiscNet& n = disc_net();
-    const DiscStash o = disc_stash(d);
+    const Stash o = disc_stash(st, d);
     const int B = d.B, T = d.T;
     int ns = 1;
     const bool ig = disc_igemm(d);           // the three stride-2 layers as implicit GEMMs: their inputs are stored phase-split (sgemm.h)
     // model.py:343-344  unsqueeze(1) -> conv 3x3 -> x*sigmoid(x)
     if (disc_out_direct() && !ex.dry) {
-        ex.fail(mcvc_disc_conv1_fwd_launch(x, P[n.conv1.wi[0]], P[n.conv1.bi[0]], st + o.c0, st + o.y0, B, 128, 80, T, ex.s, ig ? 1 : 0));
+        ex.fail(mcvc_disc_conv1_fwd_launch(x, P[n.conv1.wi[0]], P[n.conv1.bi[0]], o[DS_C0].p, o[DS_Y0].p, B, 128, 80, T, ex.s, ig ? 1 : 0));
     } else {
-        conv_fwd(ex, n.conv1, packed, B, 80, T, CView{x, 80LL * T, 80LL * T, T}, View{st + o.c0, 128LL * 80 * T, 80LL * T, T},
-                 (long long)B * 128 * 80 * T, 0, 1, &ns);
-        act_fwd(ex, st + o.c0, (long long)B * 128 * 80 * T, ns, st + o.y0, B, 128, 80 * T, ACT_SILU);
+        conv_fwd(ex, n.conv1, packed, nchw(x, B, 1, 80, T), o[DS_C0], 0, 1, &ns);
+        act_fwd(ex, o[DS_C0], ns, o[DS_Y0], ACT_SILU);
     }
-    const float* h = st + o.y0;
-    for (int i = 0; i < 3; ++i) {                       // :345-347
-        const int Ci = kDC[i], Co = kDC[i + 1], Hi = d.H[i], Wi = d.W[i], Ho = d.H[i + 1], Wo = d.W[i + 1];
-        if (ig) conv_fwd_igemm(ex, n.ds[i], packed, B, Hi, Wi, h, View{st + o.c[i], (long long)Co * Ho * Wo, (long long)Ho * Wo, Wo},
-                               (long long)B * Co * Ho * Wo, 1, &ns);
-        else conv_fwd(ex, n.ds[i], packed, B, Hi, Wi, CView{h, (long long)Ci * Hi * Wi, (long long)Hi * Wi, Wi},
-                      View{st + o.c[i], (long long)Co * Ho * Wo, (long long)Ho * Wo, Wo}, (long long)B * Co * Ho * Wo, 0, 1, &ns);
-        if (ig && i < 2) {                              // this layer's output feeds the next stride-2 layer: phase-split padded store
-            const long long pl = mcvc_xs_plane(Ho, Wo);
-            ex.y_xs_pw = mcvc_xs_pw(Wo); ex.y_xs_plane = pl;
-            norm_fwd(ex, st + o.c[i], (long long)Co * Ho * Wo, (long long)Ho * Wo, (long long)B * Co * Ho * Wo, ns, normp(P, nullptr, 4 + 4 * i, 5 + 4 * i),
-                     st + o.s[i], st + o.y[i], (long long)Co * 4 * pl, 4 * pl, Wo, nullptr, B, Co, Ho, Wo, ACT_SILU);
-        } else
-        norm_fwd(ex, st + o.c[i], (long long)Co * Ho * Wo, (long long)Ho * Wo, (long long)B * Co * Ho * Wo, ns, normp(P, nullptr, 4 + 4 * i, 5 + 4 * i),
-                 st + o.s[i], st + o.y[i], (long long)Co * Ho * Wo, (long long)Ho * Wo, Wo, nullptr, B, Co, Ho, Wo, ACT_SILU);
-        h = st + o.y[i];
+    const Tensor* h = &o[DS_Y0];
+    for (int i = 0; i < 3; ++i) {                       // :345-347  (a level's y is phase-split when it feeds the next stride-2 layer)
+        const Tensor* l = &o[DS_LEVEL + 3 * i];
+        if (ig) conv_fwd_igemm(ex, n.ds[i], packed, *h, l[L_C], 1, &ns);
+        else conv_fwd(ex, n.ds[i], packed, *h, l[L_C], 0, 1, &ns);
+        norm_fwd(ex, l[L_C], ns, normp(P, nullptr, 4 + 4 * i, 5 + 4 * i), l[L_S].p, l[L_Y], nullptr, ACT_SILU);
+        h = &l[L_Y];
     }
     // :348  1x3 conv to one channel + sigmoid
     const int H3 = d.H[3], W3 = d.W[3];
     if (disc_out_direct() && !ex.dry) {
-        ex.fail(mcvc_disc_out_fwd_launch(h, P[n.outc.wi[0]], P[n.outc.bi[0]], st + o.logit, out, B, 1024, H3, W3, ex.s));
+        ex.fail(mcvc_disc_out_fwd_launch(h->p, P[n.outc.wi[0]], P[n.outc.bi[0]], o[DS_LOGIT].p, out, B, 1024, H3, W3, ex.s));
         return;
     }
-    conv_fwd(ex, n.outc, packed, B, H3, W3, CView{h, 1024LL * H3 * W3, (long long)H3 * W3, W3}, View{st + o.logit, (long long)H3 * W3, (long long)H3 * W3, W3},
-             (long long)B * H3 * W3, 0, 1, &ns);
-    act_fwd(ex, st + o.logit, (long long)B * H3 * W3, ns, out, B, 1, H3 * W3, ACT_SIGMOID);
+    conv_fwd(ex, n.outc, packed, *h, o[DS_LOGIT], 0, 1, &ns);
+    act_fwd(ex, o[DS_LOGIT], ns, o[DS_LOGIT].at(out), ACT_SIGMOID);
 }
 
 static void disc_backward_impl(Exec& ex, const float* const* P, const float* packed, float* const* G, const float* dout, int is_logit_grad,
@@ -1847,9 +1840,8 @@ static void disc_backward_impl(Exec& ex, const float* const* P, const float* pac
 {
     ex.params = P;
     const DiscNet& n = disc_net();
-    const DiscStash o = disc_stash(d);
+    const Stash o = disc_stash(const_cast<float*>(stc), d);
     const DiscScratch q = disc_scratch(d);
-    float* st = const_cast<float*>(stc);
     const int B = d.B, T = d.T;
     float* GA = sc + q.ga;
     float* GBs[2] = {sc + q.gb, sc + q.gb2};
@@ -1860,58 +1852,38 @@ static void disc_backward_impl(Exec& ex, const float* const* P, const float* pac
     int ns = 1;
     const float* dlogit = dout;
     if (!is_logit_grad) {                         // sigmoid backward (model.py:348)
-        if (!ex.dry) {
-            ex.fail(mcvc_copy_launch(dout, GA, B * H3 * W3, ex.s));
-        }
-        act_bwd(ex, st + o.logit, GA, 0, 1, GB, B, 1, H3 * W3, ACT_SIGMOID);
+        if (!ex.dry) ex.fail(mcvc_copy_launch(dout, GA, B * H3 * W3, ex.s));
+        act_bwd(ex, o[DS_LOGIT], o[DS_LOGIT].at(GA), 1, o[DS_LOGIT].at(GB), ACT_SIGMOID);
         dlogit = GB;
     }
-    {
-        CView dyv{dlogit, (long long)H3 * W3, (long long)H3 * W3, W3};
-        CView xv{st + o.y[2], 1024LL * H3 * W3, (long long)H3 * W3, W3};
-        conv_wgrad(ex, n.outc, G, B, H3, W3, xv, dyv);
-        conv_bias_grad(ex, n.outc, G, B, dyv, H3 * W3);
-        if (disc_out_direct() && !ex.dry) ex.fail(mcvc_disc_out_dgrad_launch(dlogit, P[n.outc.wi[0]], GA, B, 1024, H3, W3, ex.s));
-        else conv_dgrad(ex, n.outc, packed, B, H3, W3, dyv, View{GA, 1024LL * H3 * W3, (long long)H3 * W3, W3}, (long long)B * 1024 * H3 * W3, 0, 1, &ns);
-    }
+    const Tensor& y2 = o[DS_LEVEL + 6 + L_Y];
+    const CTensor dlv = nchw(dlogit, B, 1, H3, W3);
+    conv_wgrad(ex, n.outc, G, y2, dlv);
+    conv_bias_grad(ex, n.outc, G, dlv);
+    if (disc_out_direct() && !ex.dry) ex.fail(mcvc_disc_out_dgrad_launch(dlogit, P[n.outc.wi[0]], GA, B, 1024, H3, W3, ex.s));
+    else conv_dgrad(ex, n.outc, packed, dlv, y2.at(GA), 0, 1, &ns);
     const bool ig = disc_igemm(d);
     for (int i = 2; i >= 0; --i) {
-        const int Ci = kDC[i], Co = kDC[i + 1], Hi = d.H[i], Wi = d.W[i], Ho = d.H[i + 1], Wo = d.W[i + 1];
+        const Tensor* l = &o[DS_LEVEL + 3 * i];
+        const Tensor& hin = (i == 0) ? o[DS_Y0] : o[DS_LEVEL + 3 * (i - 1) + L_Y];
         GB = nextGB();
-        const float* hin = (i == 0) ? (st + o.y0) : (st + o.y[i - 1]);
-        if (ig) {
-            // dY leaves the InstanceNorm backward in the padded layout the implicit data gradient gathers from (zero column / row written there);
-            // the layer's input is stored phase-split (forward): the weight gradient's staging reads both as they are
-            const int pitch = mcvc_dyp_pitch(Wo);
-            const long long pl = mcvc_dyp_plane(Ho, Wo), xpl = mcvc_xs_plane(Hi, Wi);
-            ex.dx_pitch = pitch;
-            norm_bwd(ex, st + o.c[i], (long long)Co * Ho * Wo, (long long)Ho * Wo, normp(P, G, 4 + 4 * i, 5 + 4 * i), st + o.s[i],
-                     GA, (long long)Co * Ho * Wo, (long long)Ho * Wo, Wo, (long long)B * Co * Ho * Wo, ns,
-                     GB, (long long)Co * pl, pl, pitch, 0, B, Co, Ho, Wo, ACT_SILU);
-            ex.wgrad_x_xs = 1;
-            conv_wgrad(ex, n.ds[i], G, B, Hi, Wi, CView{hin, (long long)Ci * 4 * xpl, 4 * xpl, Wi}, CView{GB, (long long)Co * pl, pl, pitch});
-            ex.wgrad_x_xs = 0;
-            conv_dgrad_igemm(ex, n.ds[i], packed, B, Hi, Wi, GB, View{GA, (long long)Ci * Hi * Wi, (long long)Hi * Wi, Wi}, (long long)B * Ci * Hi * Wi, 0, 1, &ns);
-            continue;
-        }
-        norm_bwd(ex, st + o.c[i], (long long)Co * Ho * Wo, (long long)Ho * Wo, normp(P, G, 4 + 4 * i, 5 + 4 * i), st + o.s[i],
-                 GA, (long long)Co * Ho * Wo, (long long)Ho * Wo, Wo, (long long)B * Co * Ho * Wo, ns,
-                 GB, (long long)Co * Ho * Wo, (long long)Ho * Wo, Wo, 0, B, Co, Ho, Wo, ACT_SILU);
-        CView dyv{GB, (long long)Co * Ho * Wo, (long long)Ho * Wo, Wo};
-        conv_wgrad(ex, n.ds[i], G, B, Hi, Wi, CView{hin, (long long)Ci * Hi * Wi, (long long)Hi * Wi, Wi}, dyv);
-        conv_dgrad(ex, n.ds[i], packed, B, Hi, Wi, dyv, View{GA, (long long)Ci * Hi * Wi, (long long)Hi * Wi, Wi}, (long long)B * Ci * Hi * Wi, 0, 1, &ns);
+        // implicit GEMMs: dY leaves the InstanceNorm backward in the padded layout the data gradient gathers from (zero column / row written
+        // there); the layer's input is stored phase-split (forward): the weight gradient's staging reads both as they are
+        const Tensor dyv = ig ? padded_dy(GB, B, l[L_C].C, l[L_C].H, l[L_C].W) : l[L_C].at(GB);
+        const Tensor dxv = nchw(GA, B, hin.C, hin.H, hin.W);
+        norm_bwd(ex, l[L_C], normp(P, G, 4 + 4 * i, 5 + 4 * i), l[L_S].p, l[L_C].at(GA), ns, dyv, 0, ACT_SILU);
+        conv_wgrad(ex, n.ds[i], G, hin, dyv);
+        if (ig) conv_dgrad_igemm(ex, n.ds[i], packed, dyv, dxv, 0, 1, &ns);
+        else conv_dgrad(ex, n.ds[i], packed, dyv, dxv, 0, 1, &ns);
     }
     GB = nextGB();
-    act_bwd(ex, st + o.c0, GA, (long long)B * 128 * 80 * T, ns, GB, B, 128, 80 * T, ACT_SILU);
-    {
-        CView dyv{GB, 128LL * 80 * T, 80LL * T, T};
-        // the forward input x is not in the stash; its weight gradient needs it -> caller passes it via stash? no: keep a copy
-        conv_wgrad(ex, n.conv1, G, B, 80, T, CView{st + o.total, 80LL * T, 80LL * T, T}, dyv);
-        conv_bias_grad(ex, n.conv1, G, B, dyv, 80 * T);
-        if (dx) {
-            conv_dgrad(ex, n.conv1, packed, B, 80, T, dyv, View{GA, 80LL * T, 80LL * T, T}, (long long)B * 80 * T, 0, 1, &ns);
-            if (!ex.dry) ex.fail(mcvc_mask_grad_launch(GA, ex.slabs, (long long)B * 80 * T, ns, nullptr, dx, B, 80 * T, 1, accumulate_dx, ex.s));
-        }
+    act_bwd(ex, o[DS_C0], o[DS_C0].at(GA), ns, o[DS_C0].at(GB), ACT_SILU);
+    conv_wgrad(ex, n.conv1, G, o[DS_XIN], o[DS_C0].at(GB));          // (the forward entry's copy of the input)
+    conv_bias_grad(ex, n.conv1, G, o[DS_C0].at(GB));
+    if (dx) {
+        const Tensor dxin = o[DS_XIN].at(GA);
+        conv_dgrad(ex, n.conv1, packed, o[DS_C0].at(GB), dxin, 0, 1, &ns);
+        if (!ex.dry) ex.fail(mcvc_mask_grad_launch(GA, ex.slabs, dxin.dense(), ns, nullptr, dx, B, 80 * T, 1, accumulate_dx, ex.s));
     }
     join_aux(ex);
 }
@@ -2022,7 +1994,7 @@ long long mcvc_disc_packed_floats(void) { return disc_net().packed_floats; }
 int mcvc_gen_out_frames(int T) { return gen_dims(1, T).Wu2; }
 int mcvc_disc_out_frames(int T) { return disc_dims(1, T).W[3]; }
 
-long long mcvc_gen_stash_floats(int B, int T) { return gen_stash(gen_dims(B, T)).total; }
+long long mcvc_gen_stash_floats(int B, int T) { return gen_stash(nullptr, gen_dims(B, T), B).total; }
 
 long long mcvc_gen_scratch_floats(int B, int T)
 {
@@ -2032,8 +2004,7 @@ long long mcvc_gen_scratch_floats(int B, int T)
 
 long long mcvc_disc_stash_floats(int B, int T)
 {
-    const DiscDims d = disc_dims(B, T);
-    return disc_stash(d).total + (((long long)B * 80 * T + 3) & ~3LL);   // + a copy of the input for the first layer's weight gradient
+    return disc_stash(nullptr, disc_dims(B, T)).total;          // (with the copy of the input for the first layer's weight gradient)
 }
 
 long long mcvc_disc_scratch_floats(int B, int T)
@@ -2247,12 +2218,12 @@ int mcvc_disc_update_batch(const float* const* params, const long long* numel, f
 
 // ---- host view of a pack / update plan (no device call): one row of kPlanW 64-bit integers per record (include/mcvc.h) ---------------------
 namespace {
-constexpr int kPlanW = 20;
+constexpr int kPlanW = 20, kLayoutW = 12;
 struct PlanRows {
-    long long* rows; int cap, n = 0;
+    long long* rows; int cap, w = kPlanW, n = 0;
     void put(std::initializer_list<long long> v)
     {
-        if (n < cap) { long long* r = rows + (long long)n * kPlanW; int i = 0; for (long long x : v) r[i++] = x; for (; i < kPlanW; ++i) r[i] = 0; }
+        if (n < cap) { long long* r = rows + (long long)n * w; int i = 0; for (long long x : v) r[i++] = x; for (; i < w; ++i) r[i] = 0; }
         ++n;
     }
 };
@@ -2341,6 +2312,44 @@ int mcvc_grad_store_mask(int net, int T, unsigned char* covered)
         for (int br = 0; br < c.nbr; ++br) covered[c.wi[br]] = 1;
     }
     return net == 0 ? MCVC_GEN_NPARAMS : MCVC_DISC_NPARAMS;
+}
+
+// The stash and scratch layouts of a (B, T) pass as rows of kLayoutW integers (host only, no device call; include/mcvc.h)
+int mcvc_net_layout(int net, int B, int T, int stash_B, int stash_b0, long long* rows, int cap, int* n_rows)
+{
+    if (!n_rows || (net != 0 && net != 1) || B < 1 || T < 1 || cap < 0 || (cap > 0 && !rows)) return MCVC_ERR_INVALID;
+    if (stash_B < B) stash_B = B;
+    if (stash_b0 < 0 || stash_b0 + B > stash_B || (net == 1 && stash_B != B)) return MCVC_ERR_INVALID;
+    PlanRows R{rows, cap, kLayoutW};
+    float* const base = nullptr;
+    auto stash_rows = [&](const Stash& o) {
+        for (int i = 0; i < o.n; ++i) { const Tensor& t = o[i]; R.put({1, R.n, o.off[i], o.floats[i], t.N, t.C, t.H, t.W, t.sb, t.sc, t.sh, o.win[i]}); }
+    };
+    auto raw = [&](long long off, long long n) { R.put({2, R.n, off, n, 0, 0, 0, 0, 0, 0, 0, off}); };
+    Needs nd{};
+    long long slabs = 0;
+    if (net == 0) {
+        const GenDims d = gen_dims(B, T);
+        if (d.W4 < 2 || (stash_b0 > 0 && (((long long)stash_b0 * d.W4) & 3))) return MCVC_ERR_INVALID;
+        stash_rows(gen_stash(base, d, stash_B, stash_b0));
+        const GenScratch q = gen_scratch(d);
+        auto grad = [&](long long off, int C) { const Tensor t = q.trunk(base, off, C); R.put({2, R.n, off, t.dense(), t.N, t.C, t.H, t.W, t.sb, t.sc, t.sh, off}); };
+        const int nblk = mcvc_wgrad_smallk_batch_applies(B, d.W4) ? 6 : 0;
+        raw(q.sync, 2 * MCVC_TRUNK_SYNC_WORDS); raw(q.ga, d.big); raw(q.gb, d.big); raw(q.gb2, d.big);
+        grad(q.dh, 256); grad(q.dt1, 1024); grad(q.dt1b, 1024); grad(q.dt2, 512); grad(q.dt3, 256); grad(q.dt3b, 256);
+        grad(q.dtx1, nblk * 1024); grad(q.dtx3, nblk * 256);
+        raw(q.wv, q.wino_floats); raw(q.wm, q.wino_floats); raw(q.wv2, q.wino_floats); raw(q.wm2, q.wino_floats); raw(q.wu, q.wu_floats);
+        nd = gen_needs(B, T); slabs = q.slabs;
+    } else {
+        const DiscDims d = disc_dims(B, T);
+        stash_rows(disc_stash(base, d));
+        const DiscScratch q = disc_scratch(d);
+        for (long long off : {q.ga, q.gb, q.gb2}) raw(off, d.big);
+        nd = disc_needs(B, T); slabs = q.slabs;
+    }
+    R.put({3, 0, nd.slab, nd.wslab, nd.sg, nd.sgw, slabs});
+    *n_rows = R.n;
+    return R.n > cap ? MCVC_ERR_WORKSPACE : 0;
 }
 
 int mcvc_gen_forward(const float* const* params, const float* packed, const float* x, const float* mask, float* out, float* stash,
@@ -2437,7 +2446,7 @@ int mcvc_disc_forward(const float* const* params, const float* packed, const flo
     if (ex.wslab_cap < 0) return MCVC_ERR_WORKSPACE;
     ex.fresh = get_fresh(packed);
     // keep the input for the first layer's weight gradient
-    ex.fail(mcvc_copy_launch(x, stash + disc_stash(d).total, B * 80 * T, ex.s));
+    ex.fail(mcvc_copy_launch(x, disc_stash(stash, d)[DS_XIN].p, B * 80 * T, ex.s));
     disc_forward_impl(ex, params, packed, x, out, stash, d);
     return ex.err;
 }
@@ -2705,15 +2714,14 @@ int mcvc_conv2d_forward(const float* x, const float* w, const float* bias, float
     const long long y_total = (long long)N * Cout * OH * OW;
     ex.slabs = slabs; ex.slab_cap = slabs ? (long long)(max_slabs - 1) * y_total : 0; ex.max_split = max_slabs > 0 ? max_slabs : 1;
     int ns = 1;
-    View yv = pixel_shuffle ? View{y, (long long)Cout * OH * OW, 4LL * OH * OW, 2 * OW} : View{y, (long long)Cout * OH * OW, (long long)OH * OW, OW};
+    const Tensor yv = pixel_shuffle ? nchw(y, N, Cout / 4, 2 * OH, 2 * OW) : nchw(y, N, Cout, OH, OW);
     ConvProblem p{Cin, H, W, Cout, OH, OW, KH, KW, stride, pad_h, pad_w};
-    ConvIO io{};
-    io.x = x; io.x_sb = (long long)Cin * H * W; io.x_sc = (long long)H * W; io.x_sh = W;
-    io.y = yv.p; io.y_sb = yv.sb; io.y_sc = yv.sc; io.y_sh = yv.sh; io.y_sw = 1; io.shuffle = pixel_shuffle;
+    ConvIO io = conv_io(nchw(x, N, Cin, H, W), yv);
+    io.shuffle = pixel_shuffle;
     int want = (slabs && max_slabs > 1) ? mcvc_conv_plan_nsplit(p, N, 1) : 1;
     if (want > max_slabs) want = max_slabs;
     run_conv(ex, p, N, io, y_total, wpack + c.off[PF_FWD], c.w_rows, c.cout_pk, bias ? wpack + c.off[PF_BIAS] : nullptr, 0, want, &ns);
-    if (ns > 1) act_fwd(ex, y, y_total, ns, nullptr, 1, 1, (int)y_total, ACT_NONE);
+    sum_slabs(ex, flat(y, y_total), ns);
     return ex.err;
 }
 
@@ -2729,10 +2737,9 @@ int mcvc_conv2d_dgrad(const float* dy, const float* w, float* dx, float* wpack, 
     ex.slabs = slabs; ex.slab_cap = slabs ? (long long)(max_slabs - 1) * dx_total : 0; ex.max_split = max_slabs > 0 ? max_slabs : 1;
     int ns = 1;
     // positions of dx never written by any parity class do not exist: classes tile the whole input grid
-    conv_dgrad(ex, c, wpack, N, H, W, CView{dy, (long long)Cout * OH * OW, (long long)OH * OW, OW},
-               View{dx, (long long)Cin * H * W, (long long)H * W, W}, dx_total, 0, (slabs && max_slabs > 1) ? 1 : 0, &ns);
+    conv_dgrad(ex, c, wpack, nchw(dy, N, Cout, OH, OW), nchw(dx, N, Cin, H, W), 0, (slabs && max_slabs > 1) ? 1 : 0, &ns);
     if (ns > max_slabs && !ex.err) return MCVC_ERR_WORKSPACE;
-    if (ns > 1) act_fwd(ex, dx, dx_total, ns, nullptr, 1, 1, (int)dx_total, ACT_NONE);
+    sum_slabs(ex, flat(dx, dx_total), ns);
     return ex.err;
 }
 
@@ -2792,19 +2799,16 @@ static Needs layer_needs(const ConvSpec& c, int N, int H, int W, int scheme)
     ex.wino_cap = q.wino_floats; ex.wu_cap = q.wu_floats;
     const int OH = conv_out(H, c.KH, c.stride, c.ph), OW = conv_out(W, c.KW, c.stride, c.pw);
     int ns = 1;
-    conv_fwd(ex, c, nullptr, N, H, W, CView{nullptr, (long long)c.Cin * H * W, (long long)H * W, W},
-             View{nullptr, (long long)c.cout_tot * OH * OW, (long long)OH * OW, OW}, (long long)N * c.cout_tot * OH * OW, 0, 1, &ns);
-    conv_dgrad(ex, c, nullptr, N, H, W, CView{nullptr, (long long)c.cout_tot * OH * OW, (long long)OH * OW, OW},
-               View{nullptr, (long long)c.Cin * H * W, (long long)H * W, W}, (long long)N * c.Cin * H * W, 0, 1, &ns);
-    conv_wgrad(ex, c, nullptr, N, H, W, CView{nullptr, (long long)c.Cin * H * W, (long long)H * W, W},
-               CView{nullptr, (long long)c.cout_tot * OH * OW, (long long)OH * OW, OW});
+    float* const none = nullptr;
+    const Tensor x = nchw(none, N, c.Cin, H, W), y = nchw(none, N, c.cout_tot, OH, OW);
+    conv_fwd(ex, c, nullptr, x, y, 0, 1, &ns);
+    conv_dgrad(ex, c, nullptr, y, x, 0, 1, &ns);
+    conv_wgrad(ex, c, nullptr, x, y);
     if (igemm_applies(c, H, W)) {
-        conv_fwd_igemm(ex, c, nullptr, N, H, W, nullptr, View{nullptr, (long long)c.cout_tot * OH * OW, (long long)OH * OW, OW}, (long long)N * c.cout_tot * OH * OW, 1, &ns);
-        conv_dgrad_igemm(ex, c, nullptr, N, H, W, nullptr, View{nullptr, (long long)c.Cin * H * W, (long long)H * W, W}, (long long)N * c.Cin * H * W, 0, 1, &ns);
-        ex.wgrad_x_xs = 1;             // (the implicit weight gradient's K-split slabs)
-        conv_wgrad(ex, c, nullptr, N, H, W, CView{nullptr, (long long)c.Cin * 4 * mcvc_xs_plane(H, W), 4 * mcvc_xs_plane(H, W), W},
-                   CView{nullptr, (long long)c.cout_tot * OH * OW, (long long)OH * OW, OW});
-        ex.wgrad_x_xs = 0;
+        const Tensor xs = phase_split(none, N, c.Cin, H, W);
+        conv_fwd_igemm(ex, c, nullptr, xs, y, 1, &ns);
+        conv_dgrad_igemm(ex, c, nullptr, padded_dy(none, N, c.cout_tot, OH, OW), x, 0, 1, &ns);
+        conv_wgrad(ex, c, nullptr, xs, y);             // (the implicit weight gradient's K-split slabs)
     }
     return Needs{(ex.slab_need + 3) & ~3LL, (ex.wslab_need + 3) & ~3LL, (ex.sg_need + 3) & ~3LL, (ex.sgw_need + 3) & ~3LL};
 }
@@ -2878,11 +2882,10 @@ int mcvc_layer_forward(const float* x, const float* packed, const float* w0, con
         if (err5) return err5;
         if ((long long)N * mcvc_xs_floats(Cin, H, W) > ex5.wino_cap) return MCVC_ERR_WORKSPACE;
         ex5.fail(mcvc_xs_from_dense_launch(x, ex5.wv, N, Cin, H, W, ex5.s));
-        const int OH5 = H / 2, OW5 = W / 2;
-        const long long yt = (long long)N * l.c.cout_tot * OH5 * OW5;
+        const Tensor yv5 = nchw(y, N, l.c.cout_tot, H / 2, W / 2);
         int ns5 = 1;
-        conv_fwd_igemm(ex5, l.c, packed, N, H, W, ex5.wv, View{y, (long long)l.c.cout_tot * OH5 * OW5, (long long)OH5 * OW5, OW5}, yt, 1, &ns5);
-        if (ns5 > 1) act_fwd(ex5, y, yt, ns5, nullptr, 1, 1, (int)yt, ACT_NONE);
+        conv_fwd_igemm(ex5, l.c, packed, phase_split(ex5.wv, N, Cin, H, W), yv5, 1, &ns5);
+        sum_slabs(ex5, flat(y, yv5.dense()), ns5);
         return ex5.err;
     }
     SchemeGuard sg(scheme);
@@ -2892,11 +2895,10 @@ int mcvc_layer_forward(const float* x, const float* packed, const float* w0, con
     const float* params[4] = {w0, nullptr, w1, nullptr};
     ex.params = params;
     const int OH = conv_out(H, KH, stride, pad_h), OW = conv_out(W, KW, stride, pad_w);
-    const long long y_total = (long long)N * l.c.cout_tot * OH * OW;
-    View yv = pixel_shuffle ? View{y, (long long)l.c.cout_tot * OH * OW, 4LL * OH * OW, 2 * OW} : View{y, (long long)l.c.cout_tot * OH * OW, (long long)OH * OW, OW};
+    const Tensor yv = pixel_shuffle ? nchw(y, N, l.c.cout_tot / 4, 2 * OH, 2 * OW) : nchw(y, N, l.c.cout_tot, OH, OW);
     int ns = 1;
-    conv_fwd(ex, l.c, packed, N, H, W, CView{x, (long long)Cin * H * W, (long long)H * W, W}, yv, y_total, pixel_shuffle, 1, &ns);
-    if (ns > 1) act_fwd(ex, y, y_total, ns, nullptr, 1, 1, (int)y_total, ACT_NONE);
+    conv_fwd(ex, l.c, packed, nchw(x, N, Cin, H, W), yv, pixel_shuffle, 1, &ns);
+    sum_slabs(ex, flat(y, yv.dense()), ns);
     return ex.err;
 }
 
@@ -2905,6 +2907,7 @@ int mcvc_layer_dgrad(const float* dy, const float* packed, const float* w0, cons
 {
     if (!dy || !packed || !dx || !scratch || scheme < 0 || scheme > 5 || branches < 1 || branches > 2 || (stride != 1 && stride != 2)) return MCVC_ERR_INVALID;
     const LayerCtx l = layer_ctx(Cin, Cout, branches, KH, KW, stride, pad_h, pad_w);
+    const Tensor dxv = nchw(dx, N, Cin, H, W);
     if (scheme == 5) {          // implicit GEMM: the four parity classes scattered straight into dx; the dense dY is padded first (the networks' norm_bwd writes it padded)
         if (!igemm_applies(l.c, H, W)) return MCVC_ERR_INVALID;
         int err5 = 0;
@@ -2913,10 +2916,9 @@ int mcvc_layer_dgrad(const float* dy, const float* packed, const float* w0, cons
         const int OH5 = H / 2, OW5 = W / 2;
         if ((long long)N * l.c.cout_tot * mcvc_dyp_plane(OH5, OW5) > ex5.wino_cap) return MCVC_ERR_WORKSPACE;
         ex5.fail(mcvc_dyp_from_dense_launch(dy, ex5.wm, N, l.c.cout_tot, OH5, OW5, ex5.s));
-        const long long dxt = (long long)N * Cin * H * W;
         int ns5 = 1;
-        conv_dgrad_igemm(ex5, l.c, packed, N, H, W, ex5.wm, View{dx, (long long)Cin * H * W, (long long)H * W, W}, dxt, 0, 1, &ns5);
-        if (ns5 > 1) act_fwd(ex5, dx, dxt, ns5, nullptr, 1, 1, (int)dxt, ACT_NONE);
+        conv_dgrad_igemm(ex5, l.c, packed, padded_dy(ex5.wm, N, l.c.cout_tot, OH5, OW5), dxv, 0, 1, &ns5);
+        sum_slabs(ex5, flat(dx, dxv.dense()), ns5);
         return ex5.err;
     }
     SchemeGuard sg(scheme);
@@ -2926,11 +2928,9 @@ int mcvc_layer_dgrad(const float* dy, const float* packed, const float* w0, cons
     const float* params[4] = {w0, nullptr, w1, nullptr};
     ex.params = (w0 && (branches == 1 || w1)) ? params : nullptr;         // (the staged-GEMM data gradient multiplies the OIHW tensors themselves)
     const int OH = conv_out(H, KH, stride, pad_h), OW = conv_out(W, KW, stride, pad_w);
-    const long long dx_total = (long long)N * Cin * H * W;
     int ns = 1;
-    conv_dgrad(ex, l.c, packed, N, H, W, CView{dy, (long long)l.c.cout_tot * OH * OW, (long long)OH * OW, OW},
-               View{dx, (long long)Cin * H * W, (long long)H * W, W}, dx_total, 0, 1, &ns);
-    if (ns > 1) act_fwd(ex, dx, dx_total, ns, nullptr, 1, 1, (int)dx_total, ACT_NONE);
+    conv_dgrad(ex, l.c, packed, nchw(dy, N, l.c.cout_tot, OH, OW), dxv, 0, 1, &ns);
+    sum_slabs(ex, flat(dx, dxv.dense()), ns);
     return ex.err;
 }
 
@@ -2958,11 +2958,8 @@ int mcvc_layer_wgrad_flags(const float* x, const float* dy, float* dw0, float* d
         if ((long long)N * mcvc_xs_floats(Cin, H, W) > ex5.wino_cap) return MCVC_ERR_WORKSPACE;
         ex5.fail(mcvc_xs_from_dense_launch(x, ex5.wv, N, Cin, H, W, ex5.s));
         float* grads5[4] = {dw0, nullptr, dw1, nullptr};
-        const long long xpl = mcvc_xs_plane(H, W);
-        ex5.wgrad_x_xs = 1;
         ex5.store_grads = store;
-        conv_wgrad(ex5, l.c, grads5, N, H, W, CView{ex5.wv, (long long)Cin * 4 * xpl, 4 * xpl, W},
-                   CView{dy, (long long)l.c.cout_tot * OH * OW, (long long)OH * OW, OW});
+        conv_wgrad(ex5, l.c, grads5, phase_split(ex5.wv, N, Cin, H, W), nchw(dy, N, l.c.cout_tot, OH, OW));
         return ex5.err;
     }
     SchemeGuard sg(scheme);
@@ -2971,8 +2968,7 @@ int mcvc_layer_wgrad_flags(const float* x, const float* dy, float* dw0, float* d
     if (err) return err;
     float* grads[4] = {dw0, nullptr, dw1, nullptr};
     ex.store_grads = store;
-    conv_wgrad(ex, l.c, grads, N, H, W, CView{x, (long long)Cin * H * W, (long long)H * W, W},
-               CView{dy, (long long)l.c.cout_tot * OH * OW, (long long)OH * OW, OW});
+    conv_wgrad(ex, l.c, grads, nchw(x, N, Cin, H, W), nchw(dy, N, l.c.cout_tot, OH, OW));
     return ex.err;
 }
 
@@ -3022,7 +3018,7 @@ int mcvc_instnorm_act_forward(float* x, const float* gamma, const float* beta, c
     Exec ex{}; ex.s = (hipStream_t)stream;
     NormP np{}; np.g[0] = gamma; np.b[0] = beta; np.g[1] = gamma_gate; np.b[1] = beta_gate;
     const int Cx = (act == ACT_GLU) ? 2 * C : C;
-    norm_fwd(ex, x, (long long)Cx * H * W, (long long)H * W, 0, 1, np, stats, y, (long long)C * H * W, (long long)H * W, W, residual, N, C, H, W, act);
+    norm_fwd(ex, nchw(x, N, Cx, H, W), 1, np, stats, nchw(y, N, C, H, W), residual, act);
     return ex.err;
 }
 
@@ -3034,8 +3030,7 @@ int mcvc_instnorm_act_backward(const float* x, const float* gamma, const float* 
     NormP np{}; np.g[0] = gamma; np.b[0] = beta; np.g[1] = gamma_gate; np.b[1] = beta_gate;
     np.dg[0] = dgamma; np.db[0] = dbeta; np.dg[1] = dgamma_gate; np.db[1] = dbeta_gate;
     const int Cx = (act == ACT_GLU) ? 2 * C : C;
-    norm_bwd(ex, x, (long long)Cx * H * W, (long long)H * W, np, stats, dy, (long long)C * H * W, (long long)H * W, W, 0, 1,
-             dx, (long long)Cx * H * W, (long long)H * W, W, 0, N, C, H, W, act);
+    norm_bwd(ex, nchw(x, N, Cx, H, W), np, stats, nchw(dy, N, C, H, W), 1, nchw(dx, N, Cx, H, W), 0, act);
     return ex.err;
 }
 
@@ -3076,14 +3071,15 @@ int mcvc_bias_grad(const float* dy, float* db, int N, int C, int P, void* stream
 int mcvc_act_forward(float* x, float* y, int N, int C, int P, int act, void* stream)
 {
     Exec ex{}; ex.s = (hipStream_t)stream;
-    act_fwd(ex, x, 0, 1, y, N, C, P, act);
+    act_fwd(ex, nchw(x, N, act == ACT_GLU ? 2 * C : C, 1, P), 1, nchw(y, N, C, 1, P), act);
     return ex.err;
 }
 
 int mcvc_act_backward(const float* x, float* dy, float* dx, int N, int C, int P, int act, void* stream)
 {
     Exec ex{}; ex.s = (hipStream_t)stream;
-    act_bwd(ex, x, dy, 0, 1, dx, N, C, P, act);
+    const int Cx = act == ACT_GLU ? 2 * C : C;
+    act_bwd(ex, nchw(x, N, Cx, 1, P), nchw(dy, N, C, 1, P), 1, nchw(dx, N, Cx, 1, P), act);
     return ex.err;
 }
 

@@ -98,6 +98,7 @@ _SIGS = {
     "mcvc_disc_update_batch": (c_int, [_PP, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_float, c_float, c_float, c_float, c_int, c_float, c_int, c_void_p]),
     "mcvc_pack_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "mcvc_net_layout": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),     # host only: stash / scratch layout of a pass
     "mcvc_draw_batch": (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_int, c_longlong, c_int, c_int, c_int,
                                 ctypes.c_ulonglong, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mcvc_audio_frames": (c_int, [c_int]),
