@@ -561,6 +561,43 @@ int mcvc_ms_power(const float* cep, long long n_frames, int K, const int* offs_d
 int mcvc_ms_mean_log(const float* values, int n, long long R, float floor, float* out, void* stream);
 int mcvc_ms_distance(const float* a, const float* b, int K, int n_bins, int n_used, float* per_dim, float* total, void* stream);
 
+/* ---- sample-rate conversion (new): scipy.signal.resample_poly's default filter on a bank of utterances (csrc/resample_kernels.hip;
+ *      data_preprocessing/resample.py and INTEGRATION.md restate this).  For coprime up / down, m = max(up, down), half = 10 m:
+ *      taps h[0 .. 2 half] = up * firwin(2 half + 1, 1 / m, window = ('kaiser', 5.0)) from the CALLER (float32), n_out = ceil(n_in up / down),
+ *          y[k] = sum_i x[i] h[k down + half - i up]     over the i in [0, n_in) whose tap index lies in [0, 2 half],
+ *      evaluated in polyphase form: c = k down + half, q = c div up, r = c mod up, y[k] = sum_{j < J} P[r][j] x[q - j] with
+ *      P[r][j] = h[r + j up] (zero past the last tap), J = ceil((2 half + 1) / up), x zero outside ITS utterance; fp32 fused multiply-adds in
+ *      the order j = 0 .. J - 1.  A bank is n utterances back to back in one fp32 buffer + int32 offsets [n + 1] (mcvc_audio_log_mel's layout);
+ *      one (up, down) per launch.  No atomics, no workspace, no device allocation; an utterance's result does not depend on its neighbours.
+ *        mcvc_resample_max_factor    640: the largest max(up, down).
+ *        mcvc_resample_tile_samples  1024: the most output samples of one work-list row (one workgroup).
+ *        mcvc_resample_out_samples   ceil(n_in up / down); 0 for n_in < 1 or a factor outside 1 .. 640.
+ *        mcvc_resample_table_floats  size of the packed polyphase table: up rows of an odd pitch J | 1, rounded up to 4 floats; 0 when refused.
+ *        mcvc_resample_pack          HOST -> HOST: table[r (J | 1) + j] = h[r + j up], zero elsewhere.  MCVC_ERR_INVALID: a null pointer,
+ *                                    a refused ratio, n_taps != 20 max(up, down) + 1.  The caller uploads the table (16-byte aligned).
+ *        mcvc_resample_plan          HOST tables in, HOST tables out: out_offs [n + 1] and the work list tiles [n_tiles][8] int32 = first
+ *                                    sample of the utterance in the input bank, its length, first output sample of the row in the output bank,
+ *                                    output samples of the row, q and r of the row's first output (computed in 64 bits), 0, 0.  A row holds at
+ *                                    most mcvc_resample_tile_samples() outputs, fewer where their input span would not fit in LDS.
+ *                                    tiles == NULL: only *n_tiles and out_offs are written.  MCVC_ERR_INVALID: a null pointer, n_utts < 1,
+ *                                    offsets that are negative or do not rise (an empty utterance), up == down, gcd(up, down) != 1, a factor
+ *                                    outside 1 .. 640, an output bank of 2^31 samples or more; MCVC_ERR_WORKSPACE: max_tiles too small.
+ *        mcvc_resample_run           one asynchronous launch on `stream`.  x, table (16-byte aligned), y are DEVICE pointers.  tiles is the
+ *                                    plan's table (16-byte aligned) in PINNED HOST memory (hipHostMalloc / hipHostRegister): every row is
+ *                                    checked here, on the host, and the kernel reads the same rows through the buffer's device mapping, so
+ *                                    the buffer stays alive and unchanged until the launch has finished.  MCVC_ERR_INVALID, and nothing is
+ *                                    launched: a null or misaligned pointer, tiles in memory the device cannot read, a refused ratio, a row
+ *                                    that reaches beyond [0, n_in_total) or [0, n_out_total), that holds no or too many samples, or whose
+ *                                    (q, r) are out of range.                                                                             */
+int mcvc_resample_max_factor(void);
+int mcvc_resample_tile_samples(void);
+long long mcvc_resample_out_samples(long long n_in, int up, int down);
+long long mcvc_resample_table_floats(int up, int down);
+int mcvc_resample_pack(const float* h_host, int n_taps, int up, int down, float* table_host);
+int mcvc_resample_plan(const int* in_offs, int n_utts, int up, int down, int* out_offs, int* tiles, int max_tiles, int* n_tiles);
+int mcvc_resample_run(const float* x, long long n_in_total, const int* tiles, int n_tiles, const float* table, int up, int down, float* y,
+                      long long n_out_total, void* stream);
+
 /* ---- single-op entry points (kernel parity tests; same kernels the network calls use) ---------- */
 /* y[N,Cout,OH,OW] = conv2d(x[N,Cin,H,W], w[Cout,Cin,KH,KW]) + bias ; stride 1 or 2.
  * wpack: scratch of mcvc_conv2d_pack_floats() floats, zero-initialised by the caller.

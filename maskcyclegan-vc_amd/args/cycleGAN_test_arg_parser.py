@@ -15,7 +15,12 @@ class CycleGANTestArgParser(BaseArgParser):
         ("--dtype", dict(type=str, choices=("f32", "bf16"), default="f32", help="(new) arithmetic of the generator forward: f32 (reference numerics) or bf16 MFMA.")),
         ("--wav_dir", dict(type=str, default=None, help="(new) convert the .wav files of this folder (sorted, recursive) instead of the source speaker's "
                            "preprocessed utterances: mels come from the GPU front-end (data_preprocessing/audio2mel.py) and are standardised with the source "
-                           "speaker's norm_stat.npz.  Files not at 22050 Hz are resampled with scipy.signal.resample_poly, which is not librosa's resampler.")),
+                           "speaker's norm_stat.npz.  Files not at 22050 Hz are resampled with scipy.signal.resample_poly, which is not librosa's resampler; "
+                           "--gpu_resample applies the same filter on the GPU instead.")),
+        ("--gpu_resample", dict(action="store_true", help="(new) with --wav_dir: files are read at their own rate and brought to 22050 Hz by the HIP "
+                                "polyphase resampler (data_preprocessing/resample.py: scipy's Kaiser-5.0 filter in fp32), one launch per distinct rate.")),
+        ("--out_sample_rate", dict(type=int, default=None, metavar="R", help="(new) with --vocoder_ckpt or --griffin_lim: every decoded batch is resampled "
+                                   "on the GPU from --sample_rate to R Hz before it is written; the .wav files carry rate R.")),
         ("--vocoder_ckpt", dict(type=str, default=None, help="(new) state dict of the MelGAN vocoder (torch.hub descriptinc/melgan-neurips, saved with "
                                 "torch.save): converted and original utterances are also decoded to 32-bit float .wav files under converted_audio/.  "
                                 "Without it only converted_mel/*.npy are written.")),
@@ -38,6 +43,12 @@ class CycleGANTestArgParser(BaseArgParser):
             self.parser.error("--griffin_lim and --vocoder_ckpt are two decoders for the same files: give one of them")
         if (pre.gl_mel_inverse is not None or pre.gl_mel_iter is not None) and not pre.griffin_lim:
             self.parser.error("--gl_mel_inverse and --gl_mel_iter belong to the Griffin-Lim decoder: give --griffin_lim N_ITER too")
+        if pre.out_sample_rate is not None and not (pre.vocoder_ckpt or pre.griffin_lim):
+            self.parser.error("--out_sample_rate resamples decoded audio: give --vocoder_ckpt or --griffin_lim N_ITER too")
+        if pre.out_sample_rate is not None and pre.out_sample_rate < 1:
+            self.parser.error("--out_sample_rate takes a rate in Hz >= 1")
+        if pre.gpu_resample and not pre.wav_dir:
+            self.parser.error("--gpu_resample resamples the files of --wav_dir: give --wav_dir too")
         if pre.gl_mel_iter is not None and not 0 <= pre.gl_mel_iter <= 512:
             self.parser.error("--gl_mel_iter takes a number of iterations in [0, 512]")
         self.parser.set_defaults(gl_mel_inverse="pinv", gl_mel_iter=64)

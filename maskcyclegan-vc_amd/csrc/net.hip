@@ -30,6 +30,7 @@
 #include "dtw.h"
 #include "ms.h"
 #include "f0.h"
+#include "resample.h"
 #include "../../include/mcvc.h"
 #include <string.h>
 #include <algorithm>
@@ -2674,6 +2675,31 @@ int mcvc_ms_mean_log(const float* values, int n, long long R, float floor, float
 int mcvc_ms_distance(const float* a, const float* b, int K, int n_bins, int n_used, float* per_dim, float* total, void* stream)
 {
     return mcvc_ms_distance_launch(a, b, K, n_bins, n_used, per_dim, total, (hipStream_t)stream);
+}
+
+// ---- sample-rate conversion: polyphase Kaiser filter on a bank of utterances (resample_kernels.hip) ----
+int mcvc_resample_max_factor(void) { return MCVC_RESAMPLE_MAX_FACTOR; }
+
+int mcvc_resample_tile_samples(void) { return MCVC_RESAMPLE_TILE; }
+
+long long mcvc_resample_out_samples(long long n_in, int up, int down) { return mcvc_resample_out_samples_of(n_in, up, down); }
+
+long long mcvc_resample_table_floats(int up, int down) { return mcvc_resample_table_floats_of(up, down); }
+
+int mcvc_resample_pack(const float* h_host, int n_taps, int up, int down, float* table_host)
+{
+    return mcvc_resample_pack_host(h_host, n_taps, up, down, table_host);
+}
+
+int mcvc_resample_plan(const int* in_offs, int n_utts, int up, int down, int* out_offs, int* tiles, int max_tiles, int* n_tiles)
+{
+    return mcvc_resample_plan_host(in_offs, n_utts, up, down, out_offs, tiles, max_tiles, n_tiles);
+}
+
+int mcvc_resample_run(const float* x, long long n_in_total, const int* tiles, int n_tiles, const float* table, int up, int down, float* y,
+                      long long n_out_total, void* stream)
+{
+    return mcvc_resample_run_launch(x, n_in_total, tiles, n_tiles, table, up, down, y, n_out_total, (hipStream_t)stream);
 }
 
 int mcvc_axpy(float* y, const float* x, float alpha, long long n, void* stream)

@@ -17,7 +17,8 @@ recordings are concatenated in one buffer with an offset table and come back as 
 
 ``read_wav`` follows ``librosa.load(path, sr=22050, mono=True)``: integer PCM scaled by 1 / 2^(bits-1), channels averaged; a file at
 another rate is resampled on the host with ``scipy.signal.resample_poly`` -- NOT librosa's resampler (soxr / resampy), so such files
-give close but not identical samples.  VCC2018 is recorded at 22050 Hz and never takes that branch.
+give close but not identical samples.  VCC2018 is recorded at 22050 Hz and never takes that branch.  ``read_wav_native`` stops before
+that branch and ``Audio2Mel.bank_at_rates`` applies the same filter on the device instead (data_preprocessing/resample.py).
 """
 import ctypes
 from math import gcd
@@ -89,9 +90,9 @@ def _read_with_wave_module(path):
     return rate, data.reshape(-1, ch) if ch > 1 else data
 
 
-def read_wav(path, sampling_rate=SAMPLING_RATE):
-    """-> float32 mono waveform at ``sampling_rate`` (22050 Hz), like ``librosa.load(path, sr=22050, mono=True)`` except for the
-    resampler (module docstring).  Raises ValueError for compressed, empty or unreadable files."""
+def read_wav_native(path):
+    """-> (rate, float32 mono waveform at the file's own rate): ``read_wav`` before its resampling branch.  Raises ValueError for
+    compressed, empty or unreadable files."""
     path = str(path)
     try:
         from scipy.io import wavfile
@@ -114,6 +115,13 @@ def read_wav(path, sampling_rate=SAMPLING_RATE):
         x = x.mean(axis=1, dtype=np.float32)
     if x.size == 0:
         raise ValueError("%s: no samples" % path)
+    return int(rate), x
+
+
+def read_wav(path, sampling_rate=SAMPLING_RATE):
+    """-> float32 mono waveform at ``sampling_rate`` (22050 Hz), like ``librosa.load(path, sr=22050, mono=True)`` except for the
+    resampler (module docstring).  Raises ValueError for compressed, empty or unreadable files."""
+    rate, x = read_wav_native(path)
     if int(rate) != int(sampling_rate):
         from scipy.signal import resample_poly
         g = gcd(int(sampling_rate), int(rate))
@@ -188,6 +196,34 @@ class Audio2Mel(object):
         out, fo = self._launch(wave, lengths)
         host = out.cpu().numpy()
         return [np.ascontiguousarray(host[:, fo[i]:fo[i + 1]]) for i in range(len(ws))]
+
+    def bank_at_rates(self, waveforms, rates):
+        """``bank`` for utterances recorded at different rates: waveform i is at ``rates[i]`` Hz.  Each group of equal rate is resampled
+        to 22050 Hz on the device (one launch per distinct rate, data_preprocessing/resample.py), the 22050 Hz bank is assembled on the
+        device in the caller's order and goes through the one log-mel launch; no waveform returns to the host in between."""
+        import torch
+        from data_preprocessing.resample import Resampler
+        if len(waveforms) != len(rates):
+            raise ValueError("%d waveforms but %d rates" % (len(waveforms), len(rates)))
+        if not len(waveforms):
+            return []
+        if getattr(self, "_resampler", None) is None:
+            self._resampler = Resampler(self.device)
+        groups = {}
+        for i, r in enumerate(rates):
+            groups.setdefault(int(r), []).append(i)
+        parts = [None] * len(waveforms)
+        for r, idx in groups.items():
+            dev, offs = self._resampler.bank([waveforms[i] for i in idx], r, SAMPLING_RATE)
+            for k, i in enumerate(idx):
+                parts[i] = dev[int(offs[k]):int(offs[k + 1])]
+        lengths = [int(p.numel()) for p in parts]
+        for k in lengths:
+            num_frames(k)
+        wave = torch.cat(parts) if len(parts) > 1 else parts[0].contiguous()
+        out, fo = self._launch(wave, lengths)
+        host = out.cpu().numpy()
+        return [np.ascontiguousarray(host[:, fo[i]:fo[i + 1]]) for i in range(len(parts))]
 
     def __call__(self, x):
         import torch

@@ -11,7 +11,8 @@ Utterances shorter than 64 frames are dropped like the reference does (:33).  Tw
     --data_directory <dir>   the reference's flag: <dir>/<speaker_id>/**/*.wav.  The wav -> mel step is this project's GPU front-end
                              (data_preprocessing/audio2mel.py: the same fixed transform, one launch per speaker, needs a HIP device).
                              Files that are not at 22050 Hz are resampled with scipy.signal.resample_poly, which is not librosa's
-                             resampler; VCC2018 is at 22050 Hz.
+                             resampler; VCC2018 is at 22050 Hz.  --gpu_resample applies the same filter on the GPU instead
+                             (data_preprocessing/resample.py), one launch per distinct rate.
     --mel_directory <dir>    <dir>/<speaker_id>/**/*.npy, one [80, T] mel-spectrogram per utterance from any front-end.
 
     python -m data_preprocessing.preprocess_vcc2018 --data_directory vcc2018/vcc2018_training --preprocessed_data_directory out/ --speaker_ids A B
@@ -48,13 +49,17 @@ def save_preprocessed(cache_folder, speaker_id, mel_list):
     return d
 
 
-def speaker_mels_from_wavs(data_directory, speaker_id, fft=None):
-    """Sorted <dir>/<spk>/**/*.wav -> (files, list of float32 [80, T_i]): one bank launch for the whole speaker."""
-    from .audio2mel import Audio2Mel, read_wav
+def speaker_mels_from_wavs(data_directory, speaker_id, fft=None, gpu_resample=False):
+    """Sorted <dir>/<spk>/**/*.wav -> (files, list of float32 [80, T_i]): one bank launch for the whole speaker.  ``gpu_resample``: files
+    are read at their own rate and brought to 22050 Hz on the device (``Audio2Mel.bank_at_rates``) instead of by scipy on the host."""
+    from .audio2mel import Audio2Mel, read_wav, read_wav_native
     files = sorted(glob.glob(os.path.join(data_directory, speaker_id, "**", "*.wav"), recursive=True))
     if not files:
         raise ValueError("no .wav files under %s" % os.path.join(data_directory, speaker_id))
     fft = fft or Audio2Mel()
+    if gpu_resample:
+        native = [read_wav_native(f) for f in files]
+        return files, fft.bank_at_rates([x for _, x in native], [r for r, _ in native])
     return files, fft.bank([read_wav(f) for f in files])
 
 
@@ -63,22 +68,29 @@ def build_parser():
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--data_directory", type=str, default=None,
                      help="<dir>/<speaker_id>/**/*.wav (the reference's flag); mels are computed on the GPU.  Files not at 22050 Hz are "
-                          "resampled with scipy.signal.resample_poly, which is not librosa's resampler.")
+                          "resampled with scipy.signal.resample_poly, which is not librosa's resampler; --gpu_resample applies the same filter "
+                          "on the GPU instead.")
     src.add_argument("--mel_directory", type=str, default=None, help="<dir>/<speaker_id>/**/*.npy, one [80,T] array per utterance")
     ap.add_argument("--preprocessed_data_directory", type=str, default="vcc2018_preprocessed/vcc2018_training")
     ap.add_argument("--speaker_ids", nargs="+", type=str, required=True)
+    ap.add_argument("--gpu_resample", action="store_true",
+                    help="with --data_directory: files are read at their own rate and brought to 22050 Hz by the HIP polyphase resampler "
+                         "(data_preprocessing/resample.py: scipy's Kaiser-5.0 filter in fp32)")
     return ap
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.gpu_resample and args.data_directory is None:
+        ap.error("--gpu_resample resamples .wav files: give --data_directory")
     fft = None
     for spk in args.speaker_ids:
         if args.data_directory is not None:
             if fft is None:
                 from .audio2mel import Audio2Mel
                 fft = Audio2Mel()
-            files, mels = speaker_mels_from_wavs(args.data_directory, spk, fft)
+            files, mels = speaker_mels_from_wavs(args.data_directory, spk, fft, args.gpu_resample)
         else:
             files = sorted(glob.glob(os.path.join(args.mel_directory, spk, "**", "*.npy"), recursive=True))
             mels = [np.load(f) for f in files]

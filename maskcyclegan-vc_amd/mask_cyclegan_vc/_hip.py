@@ -142,6 +142,13 @@ _SIGS = {
     "mcvc_ms_power": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mcvc_ms_mean_log": (c_int, [c_void_p, c_int, c_longlong, c_float, c_void_p, c_void_p]),
     "mcvc_ms_distance": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "mcvc_resample_max_factor": (c_int, []),
+    "mcvc_resample_tile_samples": (c_int, []),
+    "mcvc_resample_out_samples": (c_longlong, [c_longlong, c_int, c_int]),
+    "mcvc_resample_table_floats": (c_longlong, [c_int, c_int]),
+    "mcvc_resample_pack": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),                              # host only
+    "mcvc_resample_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),   # host only
+    "mcvc_resample_run": (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_longlong, c_void_p]),
     "mcvc_axpy": (c_int, [c_void_p, c_void_p, c_float, c_longlong, c_void_p]),
     "mcvc_conv2d_pack_floats": (c_longlong, [c_int, c_int, c_int, c_int]),
     "mcvc_conv2d_forward": (c_int, [c_void_p] * 6 + [c_int] * 12 + [c_void_p]),

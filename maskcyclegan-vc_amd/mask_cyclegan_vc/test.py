@@ -23,7 +23,11 @@ comes from the non-negative least-squares solver of mask_cyclegan_vc/melinv.py i
 ``pinv`` writes the files it always wrote.
 
 ``--wav_dir`` (new): the utterances to convert are the .wav files of a folder instead of the source speaker's pickle; their
-mel-spectrograms come from the GPU front-end (data_preprocessing/audio2mel.py)."""
+mel-spectrograms come from the GPU front-end (data_preprocessing/audio2mel.py).  ``--gpu_resample`` (new): files that are not at
+22050 Hz are resampled by the HIP polyphase kernel (data_preprocessing/resample.py) instead of scipy on the host.
+
+``--out_sample_rate R`` (new, with a decoder only): each decoded batch [B, 256 T] is resampled on its bucket's stream from
+``--sample_rate`` to R Hz before the copy to the host; the files carry rate R and ceil(256 T up / down) samples."""
 import os
 
 import numpy as np
@@ -63,16 +67,27 @@ class MaskCycleGANVCTesting(object):
         if self.vocoder is not None:
             self.converted_audio_dir = os.path.join(args.save_dir, args.name, "converted_audio")
             os.makedirs(self.converted_audio_dir, exist_ok=True)
+        self.out_rate = int(getattr(args, "out_sample_rate", None) or args.sample_rate)
+        self.resampler = None
+        if self.vocoder is not None and self.out_rate != int(args.sample_rate):
+            from data_preprocessing.resample import Resampler
+            from data_preprocessing.resample import ratio
+            self.resampler = Resampler(self.device)
+            self.resampler.table(*ratio(int(args.sample_rate), self.out_rate))      # uploaded once, before the two streams fork
 
     def wav_dir_utterances(self, mean, std):
         """--wav_dir: the folder's recordings (sorted) -> log-mels on the GPU (one launch) -> standardised with the SOURCE speaker's
         statistics, as the reference standardises what it feeds the generator (test.py:88-90)."""
         import glob
-        from data_preprocessing.audio2mel import Audio2Mel, read_wav
+        from data_preprocessing.audio2mel import Audio2Mel, read_wav, read_wav_native
         files = sorted(glob.glob(os.path.join(self.args.wav_dir, "**", "*.wav"), recursive=True))
         if not files:
             raise ValueError("no .wav files under %s" % self.args.wav_dir)
-        mels = Audio2Mel(self.device).bank([read_wav(f) for f in files])
+        if getattr(self.args, "gpu_resample", False):
+            native = [read_wav_native(f) for f in files]
+            mels = Audio2Mel(self.device).bank_at_rates([x for _, x in native], [r for r, _ in native])
+        else:
+            mels = Audio2Mel(self.device).bank([read_wav(f) for f in files])
         return [((m - mean) / std).astype(np.float32) for m in mels]
 
     def write_audio(self, grp, converted, original, tag, st):
@@ -80,10 +95,13 @@ class MaskCycleGANVCTesting(object):
         bucket's stream."""
         from scipy.io import wavfile
         with torch.cuda.stream(st):
-            wavs = [self.vocoder.inverse(torch.from_numpy(np.stack(m)).to(self.device)).cpu().numpy() for m in (converted, original)]
+            wavs = [self.vocoder.inverse(torch.from_numpy(np.stack(m)).to(self.device)) for m in (converted, original)]
+            if self.resampler is not None:
+                wavs = [self.resampler(w.reshape(w.shape[0], -1), int(self.args.sample_rate), self.out_rate) for w in wavs]
+            wavs = [w.cpu().numpy() for w in wavs]
         for kind, wav in zip(("converted", "original"), wavs):
             for j, i in enumerate(grp):
-                wavfile.write(os.path.join(self.converted_audio_dir, "%d-%s_%s.wav" % (i, kind, tag)), int(self.args.sample_rate), wav[j])
+                wavfile.write(os.path.join(self.converted_audio_dir, "%d-%s_%s.wav" % (i, kind, tag)), self.out_rate, wav[j])
 
     def test(self):
         a2b = self.model_name == "generator_A2B"
