@@ -598,6 +598,46 @@ int mcvc_resample_plan(const int* in_offs, int n_utts, int up, int down, int* ou
 int mcvc_resample_run(const float* x, long long n_in_total, const int* tiles, int n_tiles, const float* table, int up, int down, float* y,
                       long long n_out_total, void* stream);
 
+/* ---- silence detection (new): the frame energies librosa.effects.trim / split decide on, for a bank of utterances at 22050 Hz
+ *      (csrc/vad_kernels.hip; data_preprocessing/silence.py and INTEGRATION.md restate this; restated from librosa's published definition and
+ *      not verified against librosa).  Frame length 2048, hop 512, both fixed.  An utterance of L >= 1 samples has T = 1 + L / 512 frames;
+ *      frame t covers samples [512 t - 1024, 512 t + 1024), zero outside [0, L) of ITS utterance;
+ *          mse[t] = (1 / 2048) sum x^2   (fp32),        ref = max_t mse[t].
+ *      Frame t is non-silent iff max(mse[t], 1e-10f) > max(ref, 1e-10f) * r with r = float32(10^(-top_db / 10)): the CALLER's decision, on
+ *      the host, from the returned values (one fp32 product, one compare).  The kernel forms each 512-sample block's sum of squares once
+ *      (lane l owns samples 512 j + l + 64 i, i = 0 .. 7 in order; a butterfly of fixed shape across the wave) and a frame as
+ *      ((b0 + b1) + b2) + b3 of its four blocks, times 2^-11: one order per frame whatever shares the bank with it and wherever the
+ *      utterance starts.  The maximum is an integer atomic max on the bit pattern of the non-negative energies (no order dependence).  No
+ *      float atomic adds, no workspace, no device allocation.  A bank is n utterances back to back + int32 offsets [n + 1].
+ *        mcvc_vad_frame_length       2048.
+ *        mcvc_vad_hop                512.
+ *        mcvc_vad_tile_frames        64: the most frames of one work-list row (one workgroup).
+ *        mcvc_vad_launches           2: a memset node that zeroes ref, then the kernel, both on `stream`.
+ *        mcvc_vad_frames             1 + n / 512; 0 for n < 1.
+ *        mcvc_vad_plan               HOST tables in, HOST tables out: frame_offs [n + 1] and the work list tiles [n_tiles][4] int32 = first
+ *                                    sample of the utterance in the bank, its length, the utterance's index, first frame of the row in the
+ *                                    utterance.  tiles == NULL: only *n_tiles and frame_offs are written.  MCVC_ERR_INVALID: a null
+ *                                    pointer, n_utts < 1, offsets that are negative or do not rise (an empty utterance);
+ *                                    MCVC_ERR_WORKSPACE: max_tiles too small (*n_tiles still holds the count).
+ *        mcvc_vad_energy             asynchronous on `stream`.  wave, tiles (16-byte aligned), frame_offs_dev, mse [total_frames] and
+ *                                    ref [n_utts] are DEVICE pointers.  MCVC_ERR_INVALID, nothing launched: a null pointer, a count < 1, a
+ *                                    bank or a frame count of 2^31 or more, a misaligned pointer.  A work-list row that does not describe
+ *                                    this bank and these offsets makes its workgroup leave without reading or writing.
+ *        mcvc_audio_plan_segments    mcvc_audio_plan for segments (first sample in the bank, length) that lie anywhere in the bank, in any
+ *                                    order, overlapping or not: the same frame_offs [n + 1] and [n_tiles][4] work list for mcvc_audio_log_mel
+ *                                    (each segment is reflect-padded at its own two ends), byte-identical to mcvc_audio_plan's tables for
+ *                                    contiguous segments.  MCVC_ERR_INVALID: a null pointer, n_segs < 1, a negative start, a segment under
+ *                                    385 samples, start + length > 2^31 - 1; MCVC_ERR_WORKSPACE: max_tiles too small.                      */
+int mcvc_vad_frame_length(void);
+int mcvc_vad_hop(void);
+int mcvc_vad_tile_frames(void);
+int mcvc_vad_launches(void);
+long long mcvc_vad_frames(long long n);
+int mcvc_vad_plan(const int* sample_offs, int n_utts, int* frame_offs, int* tiles, int max_tiles, int* n_tiles);
+int mcvc_vad_energy(const float* wave, long long n_samples, const int* tiles, int n_tiles, const int* frame_offs_dev, int n_utts,
+                    float* mse, long long total_frames, float* ref, void* stream);
+int mcvc_audio_plan_segments(const int* starts, const int* lengths, int n_segs, int* frame_offs, int* tiles, int max_tiles, int* n_tiles);
+
 /* ---- single-op entry points (kernel parity tests; same kernels the network calls use) ---------- */
 /* y[N,Cout,OH,OW] = conv2d(x[N,Cin,H,W], w[Cout,Cin,KH,KW]) + bias ; stride 1 or 2.
  * wpack: scratch of mcvc_conv2d_pack_floats() floats, zero-initialised by the caller.

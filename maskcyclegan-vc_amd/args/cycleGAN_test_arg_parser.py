@@ -19,6 +19,9 @@ class CycleGANTestArgParser(BaseArgParser):
                            "--gpu_resample applies the same filter on the GPU instead.")),
         ("--gpu_resample", dict(action="store_true", help="(new) with --wav_dir: files are read at their own rate and brought to 22050 Hz by the HIP "
                                 "polyphase resampler (data_preprocessing/resample.py: scipy's Kaiser-5.0 filter in fp32), one launch per distinct rate.")),
+        ("--trim_silence", dict(type=float, default=None, metavar="TOP_DB", help="(new) with --wav_dir: every file is cut to its first .. last "
+                                "2048-sample frame within TOP_DB dB of its loudest one before it is converted (data_preprocessing/silence.py: "
+                                "librosa.effects.trim restated on the GPU, not verified against librosa).  Default: off.")),
         ("--out_sample_rate", dict(type=int, default=None, metavar="R", help="(new) with --vocoder_ckpt or --griffin_lim: every decoded batch is resampled "
                                    "on the GPU from --sample_rate to R Hz before it is written; the .wav files carry rate R.")),
         ("--vocoder_ckpt", dict(type=str, default=None, help="(new) state dict of the MelGAN vocoder (torch.hub descriptinc/melgan-neurips, saved with "
@@ -49,6 +52,9 @@ class CycleGANTestArgParser(BaseArgParser):
             self.parser.error("--out_sample_rate takes a rate in Hz >= 1")
         if pre.gpu_resample and not pre.wav_dir:
             self.parser.error("--gpu_resample resamples the files of --wav_dir: give --wav_dir too")
+        if pre.trim_silence is not None:
+            from data_preprocessing.preprocess_vcc2018 import check_silence_flags
+            check_silence_flags(self.parser, pre, "--wav_dir too", bool(pre.wav_dir))
         if pre.gl_mel_iter is not None and not 0 <= pre.gl_mel_iter <= 512:
             self.parser.error("--gl_mel_iter takes a number of iterations in [0, 512]")
         self.parser.set_defaults(gl_mel_inverse="pinv", gl_mel_iter=64)

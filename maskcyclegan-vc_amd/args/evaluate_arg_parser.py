@@ -25,6 +25,10 @@ class EvaluateArgParser(object):
         ("--f0_min", dict(type=float, default=60.0, help="With --f0: lowest F0 searched, Hz (longest lag floor(22050 / f0_min) <= 640).")),
         ("--f0_max", dict(type=float, default=500.0, help="With --f0: highest F0 searched, Hz (shortest lag ceil(22050 / f0_max) >= 2).")),
         ("--f0_threshold", dict(type=float, default=0.15, help="With --f0: YIN's threshold on the normalised difference function, in (0, 1].")),
+        ("--trim_silence", dict(type=float, default=argparse.SUPPRESS, metavar="TOP_DB", help="With --target_wav_dir: the target recordings are cut to their first "
+                                ".. last 2048-sample frame within TOP_DB dB of their loudest one (data_preprocessing/silence.py: librosa.effects.trim "
+                                "restated on the GPU, not verified against librosa) before the mel bank and the --f0 tracker see them.  Default: off (the "
+                                "parsed arguments then carry no such entry).")),
         ("--msd", dict(action="store_true", help="Also report the modulation-spectrum distance (MSD) and the global-variance distance (GVD), in dB, of "
                        "ALL converted utterances against ALL of the target speaker's: two sets, no alignment, no parallel sentences needed "
                        "(mask_cyclegan_vc/metrics.py msd).")),
@@ -49,6 +53,9 @@ class EvaluateArgParser(object):
             self.parser.error("--n_cep takes a number of coefficients in 1 .. 79")
         if args.f0 and args.target_wav_dir is None:
             self.parser.error("--f0 needs the references as audio: give --target_wav_dir (preprocessed caches hold no waveforms)")
+        if getattr(args, "trim_silence", None) is not None:
+            from data_preprocessing.preprocess_vcc2018 import check_silence_flags
+            check_silence_flags(self.parser, args, "--target_wav_dir", args.target_wav_dir is not None)
         if args.no_mcd and not args.msd:
             self.parser.error("--no_mcd leaves nothing to report: give --msd with it")
         if args.no_mcd and args.f0:

@@ -31,6 +31,7 @@
 #include "ms.h"
 #include "f0.h"
 #include "resample.h"
+#include "vad.h"
 #include "../../include/mcvc.h"
 #include <string.h>
 #include <algorithm>
@@ -2700,6 +2701,33 @@ int mcvc_resample_run(const float* x, long long n_in_total, const int* tiles, in
                       long long n_out_total, void* stream)
 {
     return mcvc_resample_run_launch(x, n_in_total, tiles, n_tiles, table, up, down, y, n_out_total, (hipStream_t)stream);
+}
+
+// ---- silence detection: frame energies of a bank of utterances (vad_kernels.hip) ----
+int mcvc_vad_frame_length(void) { return MCVC_VAD_FRAME; }
+
+int mcvc_vad_hop(void) { return MCVC_VAD_HOP; }
+
+int mcvc_vad_tile_frames(void) { return MCVC_VAD_TILE_FRAMES; }
+
+int mcvc_vad_launches(void) { return MCVC_VAD_LAUNCHES; }
+
+long long mcvc_vad_frames(long long n) { return mcvc_vad_frames_of(n); }
+
+int mcvc_vad_plan(const int* sample_offs, int n_utts, int* frame_offs, int* tiles, int max_tiles, int* n_tiles)
+{
+    return mcvc_vad_plan_host(sample_offs, n_utts, frame_offs, tiles, max_tiles, n_tiles);
+}
+
+int mcvc_vad_energy(const float* wave, long long n_samples, const int* tiles, int n_tiles, const int* frame_offs_dev, int n_utts, float* mse,
+                    long long total_frames, float* ref, void* stream)
+{
+    return mcvc_vad_energy_launch(wave, n_samples, tiles, n_tiles, frame_offs_dev, n_utts, mse, total_frames, ref, (hipStream_t)stream);
+}
+
+int mcvc_audio_plan_segments(const int* starts, const int* lengths, int n_segs, int* frame_offs, int* tiles, int max_tiles, int* n_tiles)
+{
+    return mcvc_audio_plan_segments_host(starts, lengths, n_segs, frame_offs, tiles, max_tiles, n_tiles);
 }
 
 int mcvc_axpy(float* y, const float* x, float alpha, long long n, void* stream)

@@ -183,9 +183,72 @@ class Audio2Mel(object):
                   "mcvc_audio_log_mel")
         return out, frame_offs
 
-    def bank(self, waveforms):
-        """list of 1-D waveforms (numpy or tensors, any float type) -> list of float32 numpy [80, T_i], from a single launch."""
+    def _launch_segments(self, wave, starts, lengths):
+        """``_launch`` for segments that lie anywhere in the bank ``wave``: segment i is samples [starts[i], starts[i] + lengths[i]),
+        reflect-padded at its own ends (``mcvc_audio_plan_segments``; the kernel is the same).  Nothing is copied on the device."""
         import torch
+        from mask_cyclegan_vc._hip import check, lib, ptr, stream
+        L = lib()
+        n = len(lengths)
+        if n < 1 or len(starts) != n:
+            raise ValueError("%d segment starts but %d lengths (at least one segment)" % (len(starts), n))
+        for k in lengths:
+            num_frames(k)                                              # raises for a segment under 385 samples
+        if min(starts) < 0 or max(int(s) + int(k) for s, k in zip(starts, lengths)) > wave.numel():
+            raise ValueError("a segment reaches outside the bank of %d samples" % wave.numel())
+        st, ln = np.asarray(starts, dtype=np.int32), np.asarray(lengths, dtype=np.int32)
+        frame_offs = np.zeros(n + 1, dtype=np.int32)
+        n_tiles = ctypes.c_int(0)
+        check(L.mcvc_audio_plan_segments(st.ctypes.data, ln.ctypes.data, n, frame_offs.ctypes.data, None, 0, ctypes.byref(n_tiles)), "mcvc_audio_plan_segments")
+        tiles = np.zeros((n_tiles.value, 4), dtype=np.int32)
+        check(L.mcvc_audio_plan_segments(st.ctypes.data, ln.ctypes.data, n, frame_offs.ctypes.data, tiles.ctypes.data, n_tiles.value, ctypes.byref(n_tiles)),
+              "mcvc_audio_plan_segments")
+        total = int(frame_offs[-1])
+        with torch.cuda.device(self.device):
+            tiles_d = torch.from_numpy(tiles).to(self.device)
+            out = torch.empty(N_MEL, total, dtype=torch.float32, device=self.device)
+            check(L.mcvc_audio_log_mel(ptr(wave), int(wave.numel()), ptr(tiles_d), tiles.shape[0], ptr(self.basis()), ptr(out), total, stream()),
+                  "mcvc_audio_log_mel")
+        return out, frame_offs
+
+    def _detector(self):
+        from data_preprocessing.silence import SilenceDetector
+        if getattr(self, "_silence", None) is None:
+            self._silence = SilenceDetector(self.device)
+        return self._silence
+
+    def _bank_trimmed(self, wave, lengths, trim_db, return_bounds):
+        """The 22050 Hz device bank ``wave`` -> mels of every utterance between its first and last non-silent frame
+        (data_preprocessing/silence.py), from the one log-mel launch over the trimmed segments in place."""
+        bounds = self._detector().trim(wave, trim_db, lengths=lengths)
+        offs = np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))])
+        out, fo = self._launch_segments(wave, [int(offs[i]) + s for i, (s, _) in enumerate(bounds)], [e - s for s, e in bounds])
+        host = out.cpu().numpy()
+        mels = [np.ascontiguousarray(host[:, fo[i]:fo[i + 1]]) for i in range(len(lengths))]
+        return (mels, bounds) if return_bounds else mels
+
+    def _device_bank(self, waveforms, rates=None):
+        """-> (contiguous float32 device bank at 22050 Hz, lengths): an upload, or ``bank_at_rates``' resampling."""
+        import torch
+        if rates is not None:
+            return self._resampled_bank(waveforms, rates)
+        ws = [np.ascontiguousarray(w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else w, dtype=np.float32).reshape(-1) for w in waveforms]
+        return torch.from_numpy(np.concatenate(ws)).to(self.device), [w.size for w in ws]
+
+    def bank(self, waveforms, trim_db=None, return_bounds=False):
+        """list of 1-D waveforms (numpy or tensors, any float type) -> list of float32 numpy [80, T_i], from a single launch.
+        ``trim_db`` (default None: off): every utterance is trimmed to its first .. last frame within ``trim_db`` dB of its loudest one
+        (data_preprocessing/silence.py; detection and mels from the one uploaded bank); ``return_bounds``: -> (mels, [(start, end)])."""
+        import torch
+        if trim_db is not None:
+            from data_preprocessing.silence import threshold_ratio
+            threshold_ratio(trim_db)
+            if not len(waveforms):
+                return ([], []) if return_bounds else []
+            wave, lengths = self._device_bank(waveforms)
+            for k in lengths:
+                num_frames(k)
+            return self._bank_trimmed(wave, lengths, trim_db, return_bounds)
         ws = [np.ascontiguousarray(w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else w, dtype=np.float32).reshape(-1) for w in waveforms]
         if not ws:
             return []
@@ -197,16 +260,34 @@ class Audio2Mel(object):
         host = out.cpu().numpy()
         return [np.ascontiguousarray(host[:, fo[i]:fo[i + 1]]) for i in range(len(ws))]
 
-    def bank_at_rates(self, waveforms, rates):
-        """``bank`` for utterances recorded at different rates: waveform i is at ``rates[i]`` Hz.  Each group of equal rate is resampled
-        to 22050 Hz on the device (one launch per distinct rate, data_preprocessing/resample.py), the 22050 Hz bank is assembled on the
-        device in the caller's order and goes through the one log-mel launch; no waveform returns to the host in between."""
-        import torch
-        from data_preprocessing.resample import Resampler
-        if len(waveforms) != len(rates):
+    def bank_split(self, waveforms, top_db, min_silence_ms=300.0, rates=None, return_segments=False):
+        """Long recordings -> one mel per kept interval of ``SilenceDetector.split`` (non-silent runs, merged over gaps under
+        ``min_silence_ms``, intervals under 16384 samples dropped), in file order and then time order; ``rates``: as ``bank_at_rates``.
+        ``return_segments``: -> (mels, [(start, end)] in samples of the 22050 Hz file, index of the file of each utterance,
+        {"dropped": intervals dropped per file, "samples": 22050 Hz samples per file})."""
+        from data_preprocessing.silence import gap_samples, threshold_ratio
+        threshold_ratio(top_db)
+        gap_samples(min_silence_ms)
+        if rates is not None and len(waveforms) != len(rates):
             raise ValueError("%d waveforms but %d rates" % (len(waveforms), len(rates)))
         if not len(waveforms):
-            return []
+            return ([], [], [], {"dropped": [], "samples": []}) if return_segments else []
+        wave, lengths = self._device_bank(waveforms, rates)
+        kept, dropped = self._detector().split(wave, top_db, min_silence_ms, lengths=lengths, return_dropped=True)
+        offs = np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))])
+        intervals = [iv for per_file in kept for iv in per_file]
+        index = [i for i, per_file in enumerate(kept) for _ in per_file]
+        mels = []
+        if intervals:
+            out, fo = self._launch_segments(wave, [int(offs[i]) + s for i, (s, _) in zip(index, intervals)], [e - s for s, e in intervals])
+            host = out.cpu().numpy()
+            mels = [np.ascontiguousarray(host[:, fo[i]:fo[i + 1]]) for i in range(len(intervals))]
+        return (mels, intervals, index, {"dropped": dropped, "samples": [int(k) for k in lengths]}) if return_segments else mels
+
+    def _resampled_bank(self, waveforms, rates):
+        """``bank_at_rates``' first half: -> (contiguous float32 device bank at 22050 Hz in the caller's order, lengths)."""
+        import torch
+        from data_preprocessing.resample import Resampler
         if getattr(self, "_resampler", None) is None:
             self._resampler = Resampler(self.device)
         groups = {}
@@ -218,12 +299,29 @@ class Audio2Mel(object):
             for k, i in enumerate(idx):
                 parts[i] = dev[int(offs[k]):int(offs[k + 1])]
         lengths = [int(p.numel()) for p in parts]
+        return (torch.cat(parts) if len(parts) > 1 else parts[0].contiguous()), lengths
+
+    def bank_at_rates(self, waveforms, rates, trim_db=None, return_bounds=False):
+        """``bank`` for utterances recorded at different rates: waveform i is at ``rates[i]`` Hz.  Each group of equal rate is resampled
+        to 22050 Hz on the device (one launch per distinct rate, data_preprocessing/resample.py), the 22050 Hz bank is assembled on the
+        device in the caller's order and goes through the one log-mel launch; no waveform returns to the host in between.
+        ``trim_db`` / ``return_bounds``: as ``bank``; silence is detected on the 22050 Hz bank, after resampling, and the bounds are in its
+        samples."""
+        if len(waveforms) != len(rates):
+            raise ValueError("%d waveforms but %d rates" % (len(waveforms), len(rates)))
+        if trim_db is not None:
+            from data_preprocessing.silence import threshold_ratio
+            threshold_ratio(trim_db)
+        if not len(waveforms):
+            return ([], []) if trim_db is not None and return_bounds else []
+        wave, lengths = self._resampled_bank(waveforms, rates)
         for k in lengths:
             num_frames(k)
-        wave = torch.cat(parts) if len(parts) > 1 else parts[0].contiguous()
+        if trim_db is not None:
+            return self._bank_trimmed(wave, lengths, trim_db, return_bounds)
         out, fo = self._launch(wave, lengths)
         host = out.cpu().numpy()
-        return [np.ascontiguousarray(host[:, fo[i]:fo[i + 1]]) for i in range(len(parts))]
+        return [np.ascontiguousarray(host[:, fo[i]:fo[i + 1]]) for i in range(len(lengths))]
 
     def __call__(self, x):
         import torch

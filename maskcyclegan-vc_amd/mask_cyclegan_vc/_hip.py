@@ -149,6 +149,14 @@ _SIGS = {
     "mcvc_resample_pack": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),                              # host only
     "mcvc_resample_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),   # host only
     "mcvc_resample_run": (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_longlong, c_void_p]),
+    "mcvc_vad_frame_length": (c_int, []),
+    "mcvc_vad_hop": (c_int, []),
+    "mcvc_vad_tile_frames": (c_int, []),
+    "mcvc_vad_launches": (c_int, []),
+    "mcvc_vad_frames": (c_longlong, [c_longlong]),
+    "mcvc_vad_plan": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),              # host only
+    "mcvc_vad_energy": (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, c_void_p, c_longlong, c_void_p, c_void_p]),
+    "mcvc_audio_plan_segments": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)]),  # host only
     "mcvc_axpy": (c_int, [c_void_p, c_void_p, c_float, c_longlong, c_void_p]),
     "mcvc_conv2d_pack_floats": (c_longlong, [c_int, c_int, c_int, c_int]),
     "mcvc_conv2d_forward": (c_int, [c_void_p] * 6 + [c_int] * 12 + [c_void_p]),

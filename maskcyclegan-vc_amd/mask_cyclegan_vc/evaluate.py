@@ -6,7 +6,9 @@ Inputs: the ``converted_mel/`` folder ``mask_cyclegan_vc.test`` writes (``<i>-co
 list) and the references, from one of
 
 * ``--preprocessed_data_dir`` + ``--target_speaker_id``: the target speaker's preprocessed cache, de-normalised with its norm_stat;
-* ``--target_wav_dir``: the folder's sorted .wav files through ``Audio2Mel``.
+* ``--target_wav_dir``: the folder's sorted .wav files through ``Audio2Mel``.  ``--trim_silence TOP_DB`` (with this input only) first cuts
+  every recording to its first .. last frame within TOP_DB dB of its loudest one (data_preprocessing/silence.py): the same bounds cut what
+  the mel bank and what the ``--f0`` tracker see, and ``metrics.json`` gains ``"trim_silence_db"``.
 
 Reference i must be the same sentence as source utterance i (VCC2018 is a parallel corpus; its sorted file lists line up).  That is the
 caller's contract: nothing here can check it.  An index without a reference is an error.  ``--source_speaker_id`` adds the unconverted
@@ -144,16 +146,23 @@ def evaluate(args):
     files = converted_files(args.converted_dir or os.path.join(run_dir, "converted_mel"))
     ids = [i for i, _ in files]
     converted = [np.load(p).astype(np.float32) for _, p in files]
+    trim_db = getattr(args, "trim_silence", None)                      # (absent unless the flag was given)
     if args.target_wav_dir:
         from data_preprocessing.audio2mel import Audio2Mel
         ref_waves = wav_dir_waves(args.target_wav_dir)
-        refs = Audio2Mel().bank(ref_waves)
+        if trim_db is not None:                                         # one set of bounds for the mel bank and the F0 tracker
+            refs, bounds = Audio2Mel().bank(ref_waves, trim_db=trim_db, return_bounds=True)
+            ref_waves = [w[s:e] for w, (s, e) in zip(ref_waves, bounds)]
+        else:
+            refs = Audio2Mel().bank(ref_waves)
     else:
         refs = speaker_mels(args.preprocessed_data_dir, args.target_speaker_id)
     if args.no_mcd:
         source = _pick(speaker_mels(args.preprocessed_data_dir, args.source_speaker_id), ids, "source utterance") if args.source_speaker_id else None
         utts = [{"index": i, "file": os.path.basename(p), "frames_converted": int(converted[k].shape[1])} for k, (i, p) in enumerate(files)]
         report = {"n_cep": int(args.n_cep), "n_utterances": len(utts), "utterances": utts, "msd": msd_report(args, converted, refs, source)}
+        if trim_db is not None:
+            report["trim_silence_db"] = float(trim_db)
         os.makedirs(run_dir, exist_ok=True)
         out = os.path.join(run_dir, "metrics.json")
         with open(out, "w") as fh:
@@ -196,6 +205,8 @@ def evaluate(args):
             report["f0"][key] = _stats(f0[key][keep]) if keep.any() else None
     if args.msd:
         report["msd"] = msd_report(args, converted, refs, source if base is not None else None)
+    if trim_db is not None:
+        report["trim_silence_db"] = float(trim_db)
     os.makedirs(run_dir, exist_ok=True)
     out = os.path.join(run_dir, "metrics.json")
     with open(out, "w") as fh:

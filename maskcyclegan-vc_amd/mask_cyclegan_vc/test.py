@@ -25,6 +25,8 @@ comes from the non-negative least-squares solver of mask_cyclegan_vc/melinv.py i
 ``--wav_dir`` (new): the utterances to convert are the .wav files of a folder instead of the source speaker's pickle; their
 mel-spectrograms come from the GPU front-end (data_preprocessing/audio2mel.py).  ``--gpu_resample`` (new): files that are not at
 22050 Hz are resampled by the HIP polyphase kernel (data_preprocessing/resample.py) instead of scipy on the host.
+``--trim_silence TOP_DB`` (new, with ``--wav_dir``): every file is cut to its first .. last frame within TOP_DB dB of its loudest one
+before it is converted (data_preprocessing/silence.py; the mels of the trimmed spans come from the same uploaded bank).
 
 ``--out_sample_rate R`` (new, with a decoder only): each decoded batch [B, 256 T] is resampled on its bucket's stream from
 ``--sample_rate`` to R Hz before the copy to the host; the files carry rate R and ceil(256 T up / down) samples."""
@@ -83,7 +85,13 @@ class MaskCycleGANVCTesting(object):
         files = sorted(glob.glob(os.path.join(self.args.wav_dir, "**", "*.wav"), recursive=True))
         if not files:
             raise ValueError("no .wav files under %s" % self.args.wav_dir)
-        if getattr(self.args, "gpu_resample", False):
+        trim_db = getattr(self.args, "trim_silence", None)
+        if trim_db is not None and getattr(self.args, "gpu_resample", False):
+            native = [read_wav_native(f) for f in files]
+            mels = Audio2Mel(self.device).bank_at_rates([x for _, x in native], [r for r, _ in native], trim_db=trim_db)
+        elif trim_db is not None:
+            mels = Audio2Mel(self.device).bank([read_wav(f) for f in files], trim_db=trim_db)
+        elif getattr(self.args, "gpu_resample", False):
             native = [read_wav_native(f) for f in files]
             mels = Audio2Mel(self.device).bank_at_rates([x for _, x in native], [r for r, _ in native])
         else:
